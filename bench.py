@@ -2,8 +2,19 @@
 """Benchmark of the similarity-transform round (BASELINE.json `metric`).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n N0]
-                    [--kind hilbert|random] [--dtype f64|f32] [--no-cpu]
-                    [--no-north-star] [--no-headline] [--strong] [--one-gpu]
+                    [--kind hilbert|random] [--dtype f64|f32] [--strong] [--one-gpu]
+                    [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-north-star] [--no-headline]]
+
+A plain run does what the headline figure needs and no more: it generates
+the matrix, runs W warm-up rounds, times K rounds and prints the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+workload's `config`, and at N = 1 the `roofline` of the same timed rounds).
+`--dump-outputs DIR` also writes what the last timed round left (λ, the
+eigenvector, the row sums, the matrix or a fixed seeded sample of it) as
+DIR/<name>.npy; the inputs come from fixed seeds, so two builds run with
+the same arguments can be compared file by file.  Every other leg listed
+under "Extra objects" below runs only with `--full`.
 
 One *step* = one round of the hot path on the HBM-resident matrix: the
 single fused launch (max / eigenvector update / stop test of s_k, then
@@ -27,7 +38,7 @@ of 64*N, rows split in contiguous blocks, one RCCL all-gather per round.
 `--strong` keeps n fixed instead.  `value` = algorithmic bytes of all ranks
 / max-over-ranks time (GB/s); `ms_per_step` = ms/iteration.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (`--full` only, but for the N = 1 roofline):
   roofline         the round's kernels (HIP events on the launch stream)
   round_distribution  (N = 1) per-round HIP-event times of a second pass of
                    the same schedule (first / median / max, first and last
@@ -85,6 +96,16 @@ def parse(argv=None):
     p.add_argument("--n", type=int, default=8192, help="matrix size at N=1 GPU")
     p.add_argument("--kind", default="hilbert", choices=["hilbert", "random"])
     p.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline, run every other leg: the reference-semantics "
+                        "solve, the per-round distribution, the matrix-free form, the rank "
+                        "blocks, the full-size legs, the published fp32 comparison, the CPU "
+                        "baseline and (N > 1) the overlapped exchange and configs[3]; "
+                        "the --no-* options below trim a --full run")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed round left "
+                        "(DIR/<name>.npy: eigen_val, eigen_vec, row_sums, the matrix or a "
+                        "fixed seeded sample of it)")
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--no-north-star", action="store_true",
                    help="skip the full-size legs (north_star, configs3, configs4_f32, "
@@ -432,8 +453,12 @@ def _max_over_ranks(torch, dist, world, *vals):
 CLOCKS = {}   # GPU clock levels around the headline's timed region (rank 0, N = 1)
 
 
-def timed_rounds(sh, steps, warmup, torch, dist, world, clocks_key=None):
+def timed_rounds(sh, steps, warmup, torch, dist, world, clocks_key=None, after=None,
+                 launch_pass=True):
     """Warmup + K timed rounds; returns (elapsed_s_max, kernel_ms_avg).
+    `after(sh)` runs right behind the timed region, on the state its last
+    round left (--dump-outputs); launch_pass=False leaves out the N > 1
+    per-launch pass below (kernel_ms_avg is then None).
 
     The kernel's average launch duration comes from HIP events recorded on
     the launch stream (torch's current stream, which the C-ABI launches on).
@@ -469,8 +494,12 @@ def timed_rounds(sh, steps, warmup, torch, dist, world, clocks_key=None):
     el = time.perf_counter() - t0
     if clocks_key:
         CLOCKS[clocks_key + "_after"] = gpu_clocks(torch, torch.cuda.current_device())
+    if after is not None:
+        after(sh)
     if world == 1:
         return el, ev[0][0].elapsed_time(ev[0][1]) / steps
+    if not launch_pass:
+        return _max_over_ranks(torch, dist, world, el) + (None,)
     n_ev = min(steps, 50)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
           for _ in range(n_ev)]
@@ -588,6 +617,39 @@ def cool_down(torch):
     if COOL_S > 0:
         torch.cuda.synchronize()
         time.sleep(COOL_S)
+
+
+DUMP_MATRIX_ELEMS = 1 << 22   # elements of the matrix written by --dump-outputs (<= 32 MiB)
+DUMP_SEED = 20240229          # the sample's positions: the same for every run
+
+
+def dump_outputs(path, sh, np_, torch, rank):
+    """--dump-outputs DIR: what the last timed round left on the device, i.e.
+    what a caller of the round path holds after it - λ (eigen_val), the
+    eigenvector (eigen_vec), the row sums s_{k+1} of the transformed block
+    (row_sums) and the block itself (matrix; blocks of more than
+    DUMP_MATRIX_ELEMS elements as the values at a fixed seeded set of sorted
+    flat positions) - as DIR/<name>.npy in the bench's own precision.  The
+    inputs are generated from fixed seeds, so two builds run with the same
+    arguments are comparable file by file.  Every rank takes part (the
+    eigenvector is gathered); rank 0 writes, its own block for N > 1."""
+    p = sh.part
+    torch.cuda.synchronize()
+    v = sh.eigen_vector()
+    flat = sh.mat.reshape(-1)
+    if flat.numel() > DUMP_MATRIX_ELEMS:
+        pos = np_.sort(np_.random.default_rng(DUMP_SEED).integers(
+            0, flat.numel(), size=DUMP_MATRIX_ELEMS, dtype=np_.int64))
+        flat = flat[torch.from_numpy(pos).to(flat.device)]
+    npdt = np_.float64 if sh.dtype == torch.float64 else np_.float32
+    arrays = {"eigen_val": np_.array([sh.ops.read_state(sh.state)["eigen_val"]], dtype=npdt),
+              "eigen_vec": v.cpu().numpy().astype(npdt, copy=False),
+              "row_sums": sh.s[sh.cur][:p.n].cpu().numpy().astype(npdt, copy=False),
+              "matrix": flat.cpu().numpy().astype(npdt, copy=False)}
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        for name, arr in arrays.items():
+            np_.save(os.path.join(path, name + ".npy"), arr)
 
 
 def configs3_leg(sharded, torch, dist, world, rank, steps, warmup, representative):
@@ -1122,7 +1184,13 @@ def main():
     L = _lib.load()   # fail loudly before anything else if the HIP library is missing
     if args.comm_timeout:
         L.st_set_comm_timeout(args.comm_timeout)
-    full = not args.no_north_star
+    # a plain run times the headline only; --full adds every other leg
+    full = args.full
+    big_legs = full and not args.no_north_star
+    dump = None
+    if args.dump_outputs:
+        def dump(s):
+            dump_outputs(args.dump_outputs, s, np, torch, rank)
 
     dt = torch.float64 if args.dtype == "f64" else torch.float32
     b = 8 if args.dtype == "f64" else 4
@@ -1135,22 +1203,24 @@ def main():
                  + ("library RCCL communicator" if sh.rccl is not None else "torch.distributed"))
 
     # ---- reference-semantics solve to convergence (EPS = 1e-3) ----------
-    sh.load(args.kind)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    # batch=1: the host checks the stop flag after every round, as the
-    # reference does (similarity_transform.cpp:45-50); no gated launches
-    lam, v, iters, rounds = sh.solve(eps=1e-3, max_itr=1000, batch=1)
-    torch.cuda.synchronize()
-    solve_ms = (time.perf_counter() - t0) * 1e3
-    progress(f"{workload}: solve {iters} iterations ({solve_ms:.1f} ms), world {world}")
-    solve = {"eps": 1e-3, "iter_count": iters, "rounds_evaluated": rounds,
-             "eigen_val": lam, "ms": round(solve_ms, 3)}
-    if args.kind == "hilbert" and n == 8192 and args.dtype == "f64":
-        solve["check"] = {"iter_count_expected": HILBERT8192_F64[0],
-                          "eigen_val_rel_err_vs_oracle":
-                              abs(lam - HILBERT8192_F64[1]) / HILBERT8192_F64[1]}
-    if world == 1:
+    solve = None
+    if full:
+        sh.load(args.kind)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        # batch=1: the host checks the stop flag after every round, as the
+        # reference does (similarity_transform.cpp:45-50); no gated launches
+        lam, v, iters, rounds = sh.solve(eps=1e-3, max_itr=1000, batch=1)
+        torch.cuda.synchronize()
+        solve_ms = (time.perf_counter() - t0) * 1e3
+        progress(f"{workload}: solve {iters} iterations ({solve_ms:.1f} ms), world {world}")
+        solve = {"eps": 1e-3, "iter_count": iters, "rounds_evaluated": rounds,
+                 "eigen_val": lam, "ms": round(solve_ms, 3)}
+        if args.kind == "hilbert" and n == 8192 and args.dtype == "f64":
+            solve["check"] = {"iter_count_expected": HILBERT8192_F64[0],
+                              "eigen_val_rel_err_vs_oracle":
+                                  abs(lam - HILBERT8192_F64[1]) / HILBERT8192_F64[1]}
+    if full and world == 1:
         # accuracy against the TRUE eigenvalue: Collatz–Wielandt bracket of the
         # positive input, min (A0 v)_i / v_i <= λ_true <= max (A0 v)_i / v_i
         # (torch.mv as the checker); and the same solve at eps = 1e-6
@@ -1163,13 +1233,17 @@ def main():
         del a0
 
     # ---- timed rounds ----------------------------------------------------
+    # (with N > 1 a --full run may time its headline again below, after the
+    # schedule selection: the outputs are then written behind that pass)
+    selects = full and world > 1 and not args.overlap and not args.no_overlap_leg
     sh.load(args.kind, mat=None)
     el, fused_ms = timed_rounds(sh, args.steps, args.warmup, torch, dist, world,
-                                clocks_key="headline")
+                                clocks_key="headline" if full else None,
+                                after=None if selects else dump, launch_pass=full)
     bytes_round_total = 2.0 * n * n * b
     bytes_round_local = 2.0 * p.nrows * n * b
     value = bytes_round_total * args.steps / el / 1e9
-    achieved = rate(bytes_round_local, fused_ms)
+    achieved = None if fused_ms is None else rate(bytes_round_local, fused_ms)
     progress(f"{workload}: {args.steps} timed rounds, {el / args.steps * 1e3:.4f} ms per round")
     # ---- N > 1: the same rounds with the exchange overlapped --------------
     # (split launch: local columns while the all-gather runs on a second
@@ -1182,7 +1256,7 @@ def main():
     # took the faster selection timing as the value (biased up)
     overlap_leg = None
     schedule = "overlapped" if args.overlap else "plain"
-    if world > 1 and not args.overlap and not args.no_overlap_leg:
+    if selects:
         ov = sharded.ShardedSimilarityTransform(n, dt, overlap=True)
         ov.load(args.kind)
         lam_ov, _, it_ov, _ = ov.solve(eps=1e-3, max_itr=1000, batch=1)
@@ -1211,7 +1285,7 @@ def main():
                            "eigen_val_rel_diff": abs(lam_ov - lam) / abs(lam)}
             tgt = sh
         tgt.load(args.kind)
-        el, fused_ms = timed_rounds(tgt, args.steps, args.warmup, torch, dist, world)
+        el, fused_ms = timed_rounds(tgt, args.steps, args.warmup, torch, dist, world, after=dump)
         value = bytes_round_total * args.steps / el / 1e9
         achieved = rate(bytes_round_local, fused_ms)
         overlap_leg["selection_pass"] = sel
@@ -1223,7 +1297,7 @@ def main():
 
     # ---- the per-round distribution of the same schedule (a second pass) ----
     dist_rounds = None
-    if world == 1:
+    if full and world == 1:
         dist_rounds = round_distribution(sh, args.kind, args.steps, args.warmup, torch)
         dist_rounds["headline_clocks"] = dict(CLOCKS)
         dist_rounds["headline_events_ms_per_round"] = round(fused_ms, 5)
@@ -1235,7 +1309,9 @@ def main():
     flat_pays = dev.flat_round_pays(p.nrows, n, dt)
     flat = (not use_overlap) and flat_pays
     traffic = load_traffic(workload, "k_flat" if flat else "k_round")
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+    # (a plain N > 1 run has no per-launch pass, so no kernel time to price)
+    roofline = None if achieved is None else {
+                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                 "traffic": None if traffic is None else traffic[0],
                 "kernel": (("flat split: k_flat local + k_flat remote + k_parts" if flat_pays
@@ -1251,7 +1327,7 @@ def main():
                            if world == 1 else
                            "HIP events around every launch of a 50-round pass after the timed region"),
                 "traffic_source": None if traffic is None else traffic[1]}
-    if bytes_round_local / 2 <= 2 * MALL_BYTES:
+    if roofline is not None and bytes_round_local / 2 <= 2 * MALL_BYTES:
         roofline["note"] = ("matrix partly resident in the 256 MB memory-side cache: an "
                             "effective rate, not an HBM-roofline claim (see north_star)")
     exchange = None
@@ -1270,23 +1346,25 @@ def main():
             exchange["torch_nccl_version"] = ".".join(map(str, torch.cuda.nccl.version()))
 
     # ---- the matrix-free form on the same workload (N^2*b per round) -----
-    mf = sharded.ShardedSimilarityTransform(n, dt, matrix_free=True)
-    mf.load(args.kind)
-    lam_mf, _, it_mf, _ = mf.solve(eps=1e-3, max_itr=1000, batch=1)
-    el_mf, k_mf = timed_rounds(mf, args.steps, args.warmup, torch, dist, world)
-    by_mf_local = 1.0 * p.nrows * n * b
-    tr_mf = load_traffic(workload, "k_mfree")
-    matrix_free = {"ms_per_iteration": round(el_mf / args.steps * 1e3, 5),
-                   "traffic": None if tr_mf is None else tr_mf[0],
-                   "value": round(1.0 * n * n * b * args.steps / el_mf / 1e9, 2),
-                   "kernel_ms_avg": round(k_mf, 5),
-                   "achieved": round(rate(by_mf_local, k_mf), 1),
-                   "frac": round(rate(by_mf_local, k_mf) / HBM_PEAK_GBS, 4),
-                   "bytes_per_round": 1.0 * n * n * b, "solve_iter_count": it_mf,
-                   "eigen_val": lam_mf}
-    mf.close()
-    del mf
-    progress("matrix-free leg done")
+    matrix_free = None
+    if full:
+        mf = sharded.ShardedSimilarityTransform(n, dt, matrix_free=True)
+        mf.load(args.kind)
+        lam_mf, _, it_mf, _ = mf.solve(eps=1e-3, max_itr=1000, batch=1)
+        el_mf, k_mf = timed_rounds(mf, args.steps, args.warmup, torch, dist, world)
+        by_mf_local = 1.0 * p.nrows * n * b
+        tr_mf = load_traffic(workload, "k_mfree")
+        matrix_free = {"ms_per_iteration": round(el_mf / args.steps * 1e3, 5),
+                       "traffic": None if tr_mf is None else tr_mf[0],
+                       "value": round(1.0 * n * n * b * args.steps / el_mf / 1e9, 2),
+                       "kernel_ms_avg": round(k_mf, 5),
+                       "achieved": round(rate(by_mf_local, k_mf), 1),
+                       "frac": round(rate(by_mf_local, k_mf) / HBM_PEAK_GBS, 4),
+                       "bytes_per_round": 1.0 * n * n * b, "solve_iter_count": it_mf,
+                       "eigen_val": lam_mf}
+        mf.close()
+        del mf
+        progress("matrix-free leg done")
 
     # ---- N = 1: the weak-scaled headline's per-GPU blocks at N = 2, 4, 8 --
     # (rank 0's block of n = 8192*sqrt(N), timed alone: the compute side of
@@ -1294,7 +1372,7 @@ def main():
     # (a child process too, so that a profile of this process holds the
     # headline's launches only)
     weak_blocks = None
-    if world == 1 and not args.strong and args.dtype == "f64":
+    if full and world == 1 and not args.strong and args.dtype == "f64":
         wb = child_leg("weak_rank_blocks", {
             "device": dev_index, "steps": args.steps, "warmup": args.warmup,
             "kind": args.kind, "n": args.n, "dtype": args.dtype,
@@ -1313,7 +1391,10 @@ def main():
                                           if (world == 1 and n == 8192) else
                                           f"row-block sharding over {world} GPU(s), "
                                           + ("strong" if args.strong else "weak") + "-scaled")},
-           "roofline": roofline, "solve": solve, "matrix_free": matrix_free, "rccl": rccl}
+           "full": full, "rccl": rccl}
+    for key, leg in (("roofline", roofline), ("solve", solve), ("matrix_free", matrix_free)):
+        if leg is not None:
+            out[key] = leg
     if use_overlap:
         out["config"]["exchange"] = "overlapped (split round, all-gather on a second stream)"
     if world > 1:
@@ -1338,7 +1419,7 @@ def main():
     # process of its own, the way the driver's fresh N = 1 run gets its
     # headline block; a child that fails is reported in `leg_failures`, not
     # re-run here)
-    if world == 1 and full:
+    if world == 1 and big_legs:
         sh_args = {"device": dev_index, "steps": args.steps, "warmup": args.warmup,
                    "kind": args.kind, "n": n, "dtype": args.dtype,
                    "representative": representative}
@@ -1376,7 +1457,7 @@ def main():
                 out["configs3_p1_ms_per_iteration"] = c3["ms_per_iteration"]
 
     # ---- N > 1: configs[3] strong-scaled over the world ------------------
-    if world > 1 and not args.no_configs3:
+    if full and world > 1 and not args.no_configs3:
         out["configs3_strong"] = configs3_leg(sharded, torch, dist, world, rank,
                                               max(5, min(args.steps, 20)),
                                               min(args.warmup, 3), representative)
@@ -1388,7 +1469,7 @@ def main():
     # inside the timed region); the fastest published device is a Xeon
     # Platinum 8358 at 126 ms (17 rounds).  Same call shape here: the
     # drop-in max_eigen_value on a host fp32 Hilbert matrix.
-    if world == 1 and rank == 0 and not args.no_headline:
+    if full and world == 1 and rank == 0 and not args.no_headline:
         from eigen_value_amd.similarity_transform import EigenValue
         idx = np.arange(8192, dtype=np.int64)
         h32 = np.float32(1.0) / (idx[:, None] + idx[None, :] + 1).astype(np.float32)  # utils.cpp:150
@@ -1422,7 +1503,7 @@ def main():
         out["reference_headline"]["config0_hilbert128_gpu"] = c0
 
     # ---- CPU baseline (rank 0, N = 1) ------------------------------------
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if full and world == 1 and rank == 0 and not args.no_cpu:
         cb = cpu_leg(args, np, workload, n, bytes_round_total, out["ms_per_step"])
         per_round_ms = cb.pop("_per_round_ms")
         out["cpu_baseline"] = cb

@@ -48,7 +48,7 @@ def test_committed_measurements_are_found():
 def test_bench_json_contract():
     out = subprocess.run(
         [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "1",
-         "--no-north-star", "--no-headline", "--cpu-seconds", "0.5"],
+         "--full", "--no-north-star", "--no-headline", "--cpu-seconds", "0.5"],
         capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -74,6 +74,72 @@ def test_bench_json_contract():
     assert d["solve"]["iter_count"] == 17
     assert c["affinity_cpus"] >= c["cores"] == c["threads"] >= 1 and "cpu_model" in c
     assert c["traffic_rate_3pass"] > c["value"]
+
+
+def test_plain_run_options():
+    """A plain run is the default; --full and --dump-outputs are opt-in, and
+    the options that trim a --full run still parse without it."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--no-cpu", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.no_cpu is True and a.dump_outputs == "somewhere"
+
+
+# what only a --full run measures or checks
+FULL_ONLY = ("solve", "matrix_free", "round_distribution", "weak_rank_blocks", "north_star",
+             "configs4_f32", "deferred_writes", "configs3_p1", "reference_headline",
+             "cpu_baseline", "speedup_vs_cpu")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`, twice at
+    once with the same arguments: the line holds the headline and none of
+    the --full legs, K timed steps, and DIR the last timed round's results
+    in the bench's precision, at most 64 MB, equal bit for bit between the
+    two runs (seeded inputs, a fixed sample of the matrix)."""
+    import numpy as np
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    procs = [subprocess.Popen(
+        [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5",
+         "--warmup", "1", "--dump-outputs", d],
+        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=REPO) for d in dirs]
+    outs = [pr.communicate(timeout=300) for pr in procs]
+    for pr, (so, se) in zip(procs, outs):
+        assert pr.returncode == 0, se[-4000:]
+        lines = [ln for ln in so.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, so
+        d = json.loads(lines[0])
+        assert d["full"] is False and not [k for k in FULL_ONLY if k in d]
+        assert d["steps"] == 5 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["metric"].startswith("ms/iteration") and d["unit"] == "GB/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert d["value"] > 0 and d["ms_per_step"] > 0
+        # value and ms_per_step price the same K rounds
+        assert abs(d["config"]["bytes_per_round"] / (d["ms_per_step"] * 1e6) / d["value"] - 1) < 1e-3
+        assert d["roofline"]["bound"] == "hbm" and d["roofline"]["frac"] > 0
+    got = [{f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))} for d in dirs]
+    assert sorted(got[0]) == ["eigen_val", "eigen_vec", "matrix", "row_sums"]
+    assert sum(a.nbytes for a in got[0].values()) <= 64 * 10 ** 6
+    for name, a in got[0].items():
+        assert a.dtype == np.float64 and np.all(np.isfinite(a)), name
+        assert np.array_equal(a, got[1][name]), name
+    assert got[0]["eigen_vec"].shape == got[0]["row_sums"].shape == (8192,)
+    assert got[0]["matrix"].shape == (bench.DUMP_MATRIX_ELEMS,)
+    # 6 rounds of the Hilbert iteration (1 warm-up + 5 timed) from A_0.  Each
+    # s_{k+1,i} = (A_k s_k)_i / s_k,i lies between min s_k and max s_k, so the
+    # brackets nest: the row sums of A_6 enclose the solve's λ (a row sum of
+    # A_17) and the recorded λ (s_5[0]) lies within the row sums of A_0
+    # (first row: the harmonic number H_8192; last row: H_16383 - H_8191);
+    # v is a product of factors s_k,i / max s_k <= 1
+    lam = bench.HILBERT8192_F64[1]
+    s = got[0]["row_sums"]
+    assert s.min() <= lam * (1 + 1e-12) and s.max() >= lam * (1 - 1e-12)
+    inv = 1.0 / np.arange(1, 16384, dtype=np.float64)
+    s0_max, s0_min = inv[:8192].sum(), inv[8191:].sum()
+    assert s0_min * (1 - 1e-12) <= got[0]["eigen_val"][0] <= s0_max * (1 + 1e-12)
+    assert s0_min * (1 - 1e-12) <= s.min() and s.max() <= s0_max * (1 + 1e-12)
+    assert got[0]["eigen_vec"].max() <= 1.0 and got[0]["eigen_vec"].min() > 0.0
 
 
 def test_one_gpu_lines_drop_fractions():
@@ -164,7 +230,7 @@ def test_bench_self_spawned_two_ranks_on_one_gpu():
     marked non-representative (no roofline fractions)."""
     out = subprocess.run(
         [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--one-gpu",
-         "--backend", "gloo", "--steps", "5", "--warmup", "1"],
+         "--backend", "gloo", "--steps", "5", "--warmup", "1", "--full"],
         capture_output=True, text=True, timeout=600, cwd=REPO,
         env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert out.returncode == 0, out.stderr[-4000:]
@@ -238,7 +304,7 @@ def test_bench_self_spawned_eight_ranks_on_one_gpu():
     and the configs[3] solve matches the oracle's P = 1 solve."""
     out = subprocess.run(
         [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--one-gpu",
-         "--backend", "gloo", "--steps", "5", "--warmup", "1", "--no-overlap-leg"],
+         "--backend", "gloo", "--steps", "5", "--warmup", "1", "--full", "--no-overlap-leg"],
         capture_output=True, text=True, timeout=600, cwd=REPO,
         env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert out.returncode == 0, out.stderr[-4000:]
