@@ -194,6 +194,10 @@ def _declare(L: ctypes.CDLL) -> None:
     L.max_eigen_value_f64.restype = i64
     L.max_eigen_value_ex.argtypes = [P, i32, P, P, P, u32, P, P, P]
     L.max_eigen_value_ex.restype = i64
+    L.max_eigen_value_batched_ex.argtypes = [P, i32, P, P, P, u32, u32, P, P, P]
+    L.max_eigen_value_batched_ex.restype = i64
+    L.st_solve_batched_max_dim.argtypes = [i32]
+    L.st_solve_batched_max_dim.restype = u32
     L.st_last_round_times.argtypes = [P, P, u32]
     L.st_last_round_times.restype = i32
     L.st_last_round_sums.argtypes = [P, P, u32]
@@ -209,6 +213,9 @@ def _declare(L: ctypes.CDLL) -> None:
         fn = getattr(L, f"st_solve_device_{sfx}")
         fn.argtypes = [P, P, u32, P, P, P, P, P, P]
         fn.restype = i64
+        fb = getattr(L, f"st_solve_batched_{sfx}")
+        fb.argtypes = [P, P, u32, u32, P, P, P, P, P, P, P]
+        fb.restype = i64
         getattr(L, f"st_generate_hilbert_{sfx}").argtypes = [P, u32, u32, u32, P]
         getattr(L, f"st_generate_random_{sfx}").argtypes = [P, u32, u32, u32, u64, P]
         getattr(L, f"st_generate_identity_{sfx}").argtypes = [P, u32, u32, u32, P]

@@ -2009,5 +2009,163 @@ k_solve_small(T* a, T* __restrict__ v_out, uint32_t n, T eps, uint32_t max_itr,
     v_out[threadIdx.x] = v_sh[threadIdx.x];
 }
 
+// ---------------------------------------------------------------------------
+// many small solves in ONE launch: workgroup b runs k_solve_small's whole
+// solve on matrix b of a contiguous [batch][n][n] array, writes v to
+// v_all + b n and its result to states[b].  The workgroups share nothing
+// (no atomics, no flags): each stops in its own round.
+//
+// WAVES waves per matrix (the launcher picks 4 / 8 / 16 by n, RPW <= 16 rows
+// each): row r on wave r % WAVES, lane l holding columns l W .. l W + W - 1,
+// the lane layout of k_solve_small.  Which wave holds a row changes no bit
+// (a row's sum is one lane's hsum and one wave_sum; the max is exact, and
+// the stop test is an AND), so with `vec16` (n % W == 0, 16-byte aligned base:
+// every b n n offset keeps the alignment) each entry is bit-identical to
+// k_solve_small on that matrix alone.  Without it the same layout is filled
+// by element-wide guarded loads: columns >= n hold exact zeros and their
+// column scale is 1 (the tail of both s buffers is set once), so they add
+// nothing to a row sum and stay zero under the transform.
+// ---------------------------------------------------------------------------
+template <typename T, int ORDER, int WAVES, int RPW>
+__global__ __launch_bounds__(64 * WAVES) void
+k_solve_batched(T* a_all, T* __restrict__ v_all, uint32_t n, T eps,
+                uint32_t max_itr, uint32_t semantics, st_state* states,
+                uint32_t vec16)
+{
+  constexpr int W = 16 / sizeof(T);
+  constexpr uint32_t NS = WAVES * RPW; // rows this shape holds (a multiple of W)
+  static_assert(RPW <= 64 && NS % W == 0 && NS <= small_solve_max_n<T>(),
+                "rows per wave");
+  using V = typename vec<T, W>::type;
+  __shared__ V s_sh[2][NS / W];
+  __shared__ T v_sh[NS];
+  __shared__ T inv_sh[NS]; // 1 / s_k[r], once per row instead of per lane
+  __shared__ T mx_sh[WAVES];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t nv = (n + W - 1) / W; // chunks per row (the last one ragged)
+  const bool has = lane < nv;
+  const bool cyclic = semantics == ST_SEM_SYCL;
+  T* a = a_all + (size_t)blockIdx.x * n * n;
+  T* v_out = v_all + (size_t)blockIdx.x * n;
+  st_state* state = states + blockIdx.x;
+  T* s0 = reinterpret_cast<T*>(s_sh[0]);
+  T* s1 = reinterpret_cast<T*>(s_sh[1]);
+
+  V x[RPW];
+  T t[RPW];
+#pragma unroll
+  for (int i = 0; i < RPW; i++) {
+    const uint32_t r = wave + WAVES * i;
+    x[i] = (V)(T)0;
+    if (has && r < n) {
+      if (vec16) {
+        x[i] = *reinterpret_cast<const V*>(a + (size_t)r * n + lane * W);
+      } else {
+#pragma unroll
+        for (int j = 0; j < W; j++)
+          if (lane * W + j < n)
+            x[i][j] = a[(size_t)r * n + lane * W + j];
+      }
+    }
+  }
+  // K0: s_0 = rowsum(A_0)
+#pragma unroll
+  for (int i = 0; i < RPW; i++)
+    t[i] = has ? hsum<T, W>(x[i]) : (T)0;
+  wave_sum_rows<T, RPW>(t);
+  if (lane == 63) {
+#pragma unroll
+    for (int i = 0; i < RPW; i++)
+      if (wave + WAVES * i < n)
+        s0[wave + WAVES * i] = t[i];
+  }
+  if (threadIdx.x < n)
+    v_sh[threadIdx.x] = (T)1; // initialise_eigen_vector (cpp:34)
+  else if (threadIdx.x < NS)
+    s0[threadIdx.x] = s1[threadIdx.x] = (T)1; // column scale past n (never rewritten)
+
+  T* sc_ = s0;
+  T* sn_ = s1;
+  uint32_t k = 0;
+  for (;; k++) {
+    __syncthreads(); // s_k complete
+    // m_k and stop_k (find_max starts from 0, cpp:185; cpp:413-421)
+    T mx = (T)0;
+    int ok = 1;
+    if (threadIdx.x < n) {
+      const T e0 = sc_[threadIdx.x];
+      inv_sh[threadIdx.x] = (T)1 / e0;
+      mx = e0 > mx ? e0 : mx;
+      const uint32_t nx = threadIdx.x + 1;
+      if (nx < n || cyclic) {
+        const T d = e0 - sc_[nx < n ? nx : 0];
+        ok = (d < (T)0 ? -d : d) < eps ? 1 : 0;
+      }
+    }
+    mx = wave_max(mx);
+    if (lane == 0)
+      mx_sh[wave] = mx;
+    const int stop = __syncthreads_and(ok);
+    T m = mx_sh[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; w++)
+      m = mx_sh[w] > m ? mx_sh[w] : m;
+    if (threadIdx.x < n) // cpp:260
+      v_sh[threadIdx.x] = v_sh[threadIdx.x] * (sc_[threadIdx.x] / m);
+    const bool last = stop || k + 1 >= max_itr;
+    if (last && threadIdx.x == 0) {
+      state->lambda = (double)sc_[0]; // cpp:60-65
+      state->max = (double)m;
+      state->stop = stop ? 1u : 0u;
+      state->round = k;
+      state->iters = stop ? (semantics == ST_SEM_SYCL ? k : k + 1) : max_itr;
+      state->end = k + 1;
+      state->done = 1u;
+    }
+    // A_{k+1} = D_k^-1 A_k D_k and s_{k+1} (as k_round, also in the last round)
+    const V sc = has ? reinterpret_cast<const V*>(sc_)[lane] : (V)(T)1;
+#pragma unroll
+    for (int i = 0; i < RPW; i++) {
+      const uint32_t r = wave + WAVES * i;
+      const T inv = r < n ? inv_sh[r] : (T)1;
+      if constexpr (ORDER == 0)
+        x[i] = x[i] * (inv * sc); // cpp:324-325
+      else
+        x[i] = (inv * x[i]) * sc; // main.py:13-16
+      t[i] = has ? hsum<T, W>(x[i]) : (T)0;
+    }
+    wave_sum_rows<T, RPW>(t);
+    if (lane == 63) {
+#pragma unroll
+      for (int i = 0; i < RPW; i++)
+        if (wave + WAVES * i < n)
+          sn_[wave + WAVES * i] = t[i];
+    }
+    T* tmp = sc_;
+    sc_ = sn_;
+    sn_ = tmp;
+    if (last)
+      break;
+  }
+  // write back: the transformed matrix and v
+#pragma unroll
+  for (int i = 0; i < RPW; i++) {
+    const uint32_t r = wave + WAVES * i;
+    if (has && r < n) {
+      if (vec16) {
+        *reinterpret_cast<V*>(a + (size_t)r * n + lane * W) = x[i];
+      } else {
+#pragma unroll
+        for (int j = 0; j < W; j++)
+          if (lane * W + j < n)
+            a[(size_t)r * n + lane * W + j] = x[i][j];
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < n)
+    v_out[threadIdx.x] = v_sh[threadIdx.x];
+}
+
 } // namespace dev
 } // namespace st

@@ -132,5 +132,14 @@ bool solve_small_fits(const T* a, uint32_t n);
 template <typename T>
 int launch_solve_small(T* a, T* v, uint32_t n, T eps, uint32_t max_itr,
                        uint32_t semantics, st_state* st, hipStream_t stream);
+// the same solve for every matrix of a contiguous [batch][n][n] array in one
+// launch (k_solve_batched, a workgroup per matrix): v to v + b n, the result
+// to st[b]; any n from 1 to solve_batched_max_n (128 fp64 / 256 fp32)
+template <typename T>
+uint32_t solve_batched_max_n();
+template <typename T>
+int launch_solve_batched(T* a, T* v, uint32_t batch, uint32_t n, T eps,
+                         uint32_t max_itr, uint32_t semantics, st_state* st,
+                         hipStream_t stream);
 
 } // namespace st

@@ -1566,6 +1566,70 @@ launch_solve_small(T* a, T* v, uint32_t n, T eps, uint32_t max_itr,
   return check_launch("solve_small");
 }
 
+template <typename T>
+uint32_t
+solve_batched_max_n()
+{
+  return dev::small_solve_max_n<T>();
+}
+
+// workgroup shape per n: the fewest waves (4 / 8 / 16) that hold the matrix
+// at <= 16 rows each, rows per wave the power of two >= ceil(n / waves)
+template <typename T>
+int
+launch_solve_batched(T* a, T* v, uint32_t batch, uint32_t n, T eps,
+                     uint32_t max_itr, uint32_t semantics, st_state* st,
+                     hipStream_t stream)
+{
+  constexpr uint32_t W = 16 / sizeof(T);
+  ST_REQUIRE(a && v && st, "solve_batched: null pointer");
+  ST_REQUIRE(n > 0 && n <= solve_batched_max_n<T>(),
+             "solve_batched: n = %u does not fit one workgroup", n);
+  ST_REQUIRE(batch > 0 && batch <= 0x7fffffffu,
+             "solve_batched: batch = %u outside 1 .. 2^31 - 1", batch);
+  ST_REQUIRE(semantics <= ST_SEM_MAINPY, "solve_batched: bad semantics %u",
+             semantics);
+  ST_REQUIRE(max_itr > 0, "solve_batched: max_itr must be > 0");
+  const uint32_t vec = (n % W == 0 && aligned16(a)) ? 1u : 0u;
+  auto go = [&](auto order, auto waves, auto rpw) {
+    constexpr int WV = decltype(waves)::value;
+    hipLaunchKernelGGL(
+      (dev::k_solve_batched<T, decltype(order)::value, WV, decltype(rpw)::value>),
+      dim3(batch), dim3(64 * WV), 0, stream, a, v, n, eps, max_itr, semantics,
+      st, vec);
+  };
+  auto by_shape = [&](auto order) {
+    using std::integral_constant;
+    if (n <= 4)
+      go(order, integral_constant<int, 4>{}, integral_constant<int, 1>{});
+    else if (n <= 8)
+      go(order, integral_constant<int, 4>{}, integral_constant<int, 2>{});
+    else if (n <= 16)
+      go(order, integral_constant<int, 4>{}, integral_constant<int, 4>{});
+    else if (n <= 32)
+      go(order, integral_constant<int, 4>{}, integral_constant<int, 8>{});
+    else if (n <= 64)
+      go(order, integral_constant<int, 4>{}, integral_constant<int, 16>{});
+    else if (n <= 128)
+      go(order, integral_constant<int, 8>{}, integral_constant<int, 16>{});
+    else if constexpr (sizeof(T) == 4)
+      go(order, integral_constant<int, 16>{}, integral_constant<int, 16>{});
+  };
+  if (semantics == ST_SEM_MAINPY)
+    by_shape(std::integral_constant<int, 1>{});
+  else
+    by_shape(std::integral_constant<int, 0>{});
+  return check_launch("solve_batched");
+}
+
+template uint32_t solve_batched_max_n<float>();
+template uint32_t solve_batched_max_n<double>();
+template int launch_solve_batched<float>(float*, float*, uint32_t, uint32_t,
+                                         float, uint32_t, uint32_t, st_state*,
+                                         hipStream_t);
+template int launch_solve_batched<double>(double*, double*, uint32_t, uint32_t,
+                                          double, uint32_t, uint32_t,
+                                          st_state*, hipStream_t);
 template bool solve_small_fits<float>(const float*, uint32_t);
 template bool solve_small_fits<double>(const double*, uint32_t);
 template int launch_solve_small<float>(float*, float*, uint32_t, float,

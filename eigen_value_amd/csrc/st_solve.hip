@@ -84,6 +84,10 @@ struct Context
   std::vector<unsigned char> trace;
   uint32_t trace_rounds = 0;
   hipEvent_t ev_flag[2] = { nullptr, nullptr };
+  // batched solve: one st_state per matrix (device array and its host copy)
+  st_state* d_bstate = nullptr;
+  size_t bstate_cap = 0; // states
+  std::vector<st_state> h_bstate;
 };
 
 double
@@ -166,6 +170,22 @@ ensure_trace(Context* c, size_t bytes)
   }
   ST_CHECK(hipMalloc(&c->d_trace, bytes));
   c->trace_cap = bytes;
+  return 0;
+}
+
+int
+ensure_bstate(Context* c, size_t count)
+{
+  if (c->d_bstate && c->bstate_cap >= count)
+    return 0;
+  if (c->d_bstate) {
+    ST_CHECK(hipStreamSynchronize(c->stream));
+    ST_CHECK(hipFree(c->d_bstate));
+    c->d_bstate = nullptr;
+    c->bstate_cap = 0;
+  }
+  ST_CHECK(hipMalloc((void**)&c->d_bstate, count * sizeof(st_state)));
+  c->bstate_cap = count;
   return 0;
 }
 
@@ -483,6 +503,129 @@ solve_host(Context* c, const T* mat, uint32_t n, T* eigen_val, T* eigen_vec,
   return (int64_t)(h2d + local.loop_ms);
 }
 
+// what both batched entry points reject before touching the device
+template <typename T>
+int
+batched_args(Context* c, uint32_t batch, uint32_t n, const st_options* opt,
+             Resolved* o)
+{
+  ST_REQUIRE(c, "null queue");
+  if (resolve<T>(opt, o))
+    return -1;
+  constexpr uint32_t kNoBatch = ST_FLAG_MATRIX_FREE | ST_FLAG_TIME_KERNELS |
+                                ST_FLAG_TRACE_SUMS | ST_FLAG_ROUND_LOOP;
+  ST_REQUIRE((o->flags & kNoBatch) == 0,
+             "batched solve: ST_FLAG_MATRIX_FREE, ST_FLAG_TIME_KERNELS, "
+             "ST_FLAG_TRACE_SUMS and ST_FLAG_ROUND_LOOP are not supported "
+             "(flags = %u)", o->flags);
+  ST_REQUIRE(n > 0, "dim must be > 0");
+  ST_REQUIRE(n <= solve_batched_max_n<T>(),
+             "batched solve: dim = %u exceeds the one-workgroup limit %u "
+             "(st_solve_batched_max_dim)", n, solve_batched_max_n<T>());
+  ST_REQUIRE(batch <= 0x7fffffffu,
+             "batched solve: batch = %u exceeds the grid limit 2^31 - 1", batch);
+  return 0;
+}
+
+// Many small solves in one launch (k_solve_batched: a workgroup per matrix
+// of the device-resident [batch][n][n] array, each transformed in place).
+// One memset of the state array, one launch, one stream sync, one read-back.
+template <typename T>
+int64_t
+solve_batched(Context* c, T* d_mats, uint32_t batch, uint32_t n, T* d_v_out,
+              T* v_host, T* eigen_vals, uint32_t* iter_cnts,
+              uint32_t* converged, const st_options* opt, st_stats* stats)
+{
+  Resolved o;
+  if (batched_args<T>(c, batch, n, opt, &o))
+    return -1;
+  if (stats)
+    std::memset(stats, 0, sizeof(*stats));
+  if (batch == 0) { // nothing to solve
+    if (stats)
+      stats->converged = 1;
+    return 0;
+  }
+  ST_REQUIRE(d_mats, "null matrix");
+  ST_REQUIRE(eigen_vals && iter_cnts, "null output pointer");
+  ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
+  const size_t v_bytes = sizeof(T) * (size_t)batch * n;
+  if (ensure_device(c) || ensure_bstate(c, batch) ||
+      (!d_v_out && ensure_part(c, v_bytes))) // d_part: free outside flat rounds
+    return -1;
+  T* d_v = d_v_out ? d_v_out : reinterpret_cast<T*>(c->d_part);
+  hipStream_t s = c->stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)batch, s));
+  if (launch_solve_batched<T>(d_mats, d_v, batch, n, (T)o.eps, o.max_itr,
+                              o.semantics, c->d_bstate, s))
+    return -1;
+  ST_CHECK(hipStreamSynchronize(s));
+  c->h_bstate.resize(batch);
+  ST_CHECK(hipMemcpy(c->h_bstate.data(), c->d_bstate,
+                     sizeof(st_state) * (size_t)batch, hipMemcpyDeviceToHost));
+  const double loop_ms = ms_since(t0);
+
+  const auto t1 = std::chrono::steady_clock::now();
+  uint32_t rounds = 0, all = 1;
+  for (uint32_t b = 0; b < batch; b++) {
+    const st_state& fin = c->h_bstate[b];
+    ST_REQUIRE(fin.done, "internal: matrix %u ended without done flag", b);
+    eigen_vals[b] = (T)fin.lambda;
+    iter_cnts[b] = fin.iters;
+    if (converged)
+      converged[b] = fin.stop;
+    rounds = fin.end > rounds ? fin.end : rounds;
+    all &= fin.stop;
+  }
+  if (v_host)
+    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
+  const double d2h_ms = ms_since(t1);
+  if (stats) {
+    stats->loop_ms = loop_ms;
+    stats->d2h_ms = d2h_ms;
+    stats->rounds = rounds;
+    stats->converged = all;
+  }
+  return (int64_t)loop_ms;
+}
+
+// host-pointer twin: [mats | v] staged in the context's matrix buffer
+template <typename T>
+int64_t
+solve_batched_host(Context* c, const T* mats, uint32_t batch, uint32_t n,
+                   T* eigen_vals, T* eigen_vecs, uint32_t* iter_cnts,
+                   const st_options* opt, st_stats* stats)
+{
+  Resolved o;
+  if (batched_args<T>(c, batch, n, opt, &o))
+    return -1;
+  if (batch == 0) // the no-op, with its stats
+    return solve_batched<T>(c, nullptr, 0, n, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, opt, stats);
+  ST_REQUIRE(mats && eigen_vals && eigen_vecs && iter_cnts, "null pointer");
+  const size_t bytes =
+    (sizeof(T) * (size_t)batch * n * n + 255) & ~(size_t)255; // v stays aligned
+  if (ensure_device(c) ||
+      ensure_matrix(c, bytes + sizeof(T) * (size_t)batch * n))
+    return -1;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(c->d_mat, mats, sizeof(T) * (size_t)batch * n * n,
+                          hipMemcpyHostToDevice, c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  const double h2d = ms_since(t0);
+  T* d_mats = reinterpret_cast<T*>(c->d_mat);
+  T* d_v = reinterpret_cast<T*>((char*)c->d_mat + bytes);
+  st_stats local{};
+  if (solve_batched<T>(c, d_mats, batch, n, d_v, eigen_vecs, eigen_vals,
+                       iter_cnts, nullptr, opt, &local) < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
+}
+
 Context*
 as_ctx(void* wq)
 {
@@ -583,6 +726,8 @@ destroy_queue(void* wq)
     (void)hipFree(c->d_trace);
   if (c->d_state)
     (void)hipFree(c->d_state);
+  if (c->d_bstate)
+    (void)hipFree(c->d_bstate);
   if (c->h_state)
     (void)hipHostFree(c->h_state);
   for (hipEvent_t e : c->ev_flag)
@@ -707,6 +852,63 @@ st_solve_device_f64(void* wq, double* d_mat, unsigned int dim,
   return st::solve_device<double>(st::as_ctx(wq), d_mat, dim, d_eigen_vec,
                                   eigen_vec_host, eigen_val, iter_cnt, opt,
                                   stats);
+}
+
+int64_t
+st_solve_batched_f32(void* wq, float* d_mats, unsigned int batch,
+                     unsigned int dim, float* d_eigen_vecs,
+                     float* eigen_vecs_host, float* eigen_vals,
+                     unsigned int* iter_cnts, unsigned int* converged,
+                     const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_batched<float>(st::as_ctx(wq), d_mats, batch, dim,
+                                  d_eigen_vecs, eigen_vecs_host, eigen_vals,
+                                  iter_cnts, converged, opt, stats);
+}
+
+int64_t
+st_solve_batched_f64(void* wq, double* d_mats, unsigned int batch,
+                     unsigned int dim, double* d_eigen_vecs,
+                     double* eigen_vecs_host, double* eigen_vals,
+                     unsigned int* iter_cnts, unsigned int* converged,
+                     const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_batched<double>(st::as_ctx(wq), d_mats, batch, dim,
+                                   d_eigen_vecs, eigen_vecs_host, eigen_vals,
+                                   iter_cnts, converged, opt, stats);
+}
+
+int64_t
+max_eigen_value_batched_ex(void* wq, int dtype, const void* mats,
+                           void* eigen_vals, void* eigen_vecs,
+                           unsigned int batch, unsigned int dim,
+                           unsigned int* iter_cnts, const st_options* opt,
+                           st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (dtype == 0)
+    return st::solve_batched_host<float>(
+      st::as_ctx(wq), (const float*)mats, batch, dim, (float*)eigen_vals,
+      (float*)eigen_vecs, iter_cnts, opt, stats);
+  if (dtype == 1)
+    return st::solve_batched_host<double>(
+      st::as_ctx(wq), (const double*)mats, batch, dim, (double*)eigen_vals,
+      (double*)eigen_vecs, iter_cnts, opt, stats);
+  st::set_error("max_eigen_value_batched_ex: dtype must be 0 (f32) or 1 (f64)");
+  return -1;
+}
+
+unsigned int
+st_solve_batched_max_dim(int dtype)
+{
+  return dtype == 0   ? st::solve_batched_max_n<float>()
+         : dtype == 1 ? st::solve_batched_max_n<double>()
+                      : 0u;
 }
 
 } // extern "C"

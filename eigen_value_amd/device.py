@@ -346,6 +346,16 @@ def epilogue(s, v, state, eps: float, max_itr: int = _lib.ST_MAX_ITR,
 # --------------------------------------------------------------------------
 # whole solve on a device-resident matrix
 # --------------------------------------------------------------------------
+def batched_max_dim(dtype) -> int:
+    """Largest n ``DeviceSolver.solve_batched`` accepts for ``dtype`` (torch
+    or numpy float32 / float64): 256 / 128 (st_solve_batched_max_dim)."""
+    name = str(dtype).split(".")[-1].strip("'>")
+    if name not in ("float32", "float64"):
+        raise TypeError(f"float32/float64 required, got {dtype}")
+    return int(_lib.load().st_solve_batched_max_dim(1 if name == "float64" else 0))
+
+
+
 class DeviceSolver:
     """Owns one library context bound to the current torch stream."""
 
@@ -416,6 +426,51 @@ class DeviceSolver:
             ctypes.byref(opt), ctypes.byref(stats))
         _lib.check(rc, "st_solve_device")
         return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def solve_batched(self, mats, *, inplace: bool = False, eps: Optional[float] = None,
+                      max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL):
+        """Many small matrices in ONE launch, a workgroup per matrix
+        (``st_solve_batched_*``).  ``mats``: a torch tensor or DLPack producer
+        of shape (B, n, n) on this solver's device, n <= ``batched_max_dim``.
+
+        Returns (λ: host tensor[B], v: device tensor[B, n], iterations: host
+        tensor[B] (int64), stats: dict).  ``stats["converged_each"]`` is a
+        uint32 array[B]; ``stats["rounds"]`` the largest round count of the
+        batch and ``stats["converged"]`` 1 only if every matrix converged.
+
+        For n % (16 / element size) == 0 every entry equals ``solve`` on that
+        matrix alone bit for bit (λ, v, count and, with ``inplace``, the
+        final matrix); other n agree to rounding.  ``inplace`` transforms
+        ``mats`` itself (it must be contiguous); otherwise a copy is made."""
+        import numpy as np
+        torch = _torch()
+        if not isinstance(mats, torch.Tensor) and hasattr(mats, "__dlpack__"):
+            mats = torch.from_dlpack(mats)   # any DLPack producer, zero copy
+        _check_cuda(mats)
+        if mats.device.index != (self.device.index if self.device.index is not None
+                                 else torch.cuda.current_device()):
+            raise ValueError(f"matrices on {mats.device}, solver context on {self.device}")
+        assert mats.dim() == 3 and mats.shape[1] == mats.shape[2], "must be (B, n, n)"
+        sfx = _sfx(mats)
+        b, n = mats.shape[0], mats.shape[1]
+        if inplace and not mats.is_contiguous():
+            raise ValueError("inplace needs a contiguous (B, n, n) tensor")
+        work = (mats if inplace else mats.clone()).contiguous()
+        v = torch.empty((b, n), dtype=mats.dtype, device=mats.device)
+        npdt = np.float64 if mats.dtype == torch.float64 else np.float32
+        lam = np.zeros(b, dtype=npdt)
+        it = np.zeros(b, dtype=np.uint32)
+        conv = np.zeros(b, dtype=np.uint32)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics, 0, 0)
+        stats = _lib.st_stats()
+        _lib.check(self.L.st_set_stream(self.q, _stream(mats.device)), "st_set_stream")
+        rc = getattr(self.L, f"st_solve_batched_{sfx}")(
+            self.q, _ptr(work), b, n, _ptr(v), None, lam.ctypes.data, it.ctypes.data,
+            conv.ctypes.data, ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(rc, "st_solve_batched")
+        out = stats.as_dict()
+        out["converged_each"] = conv
+        return (torch.from_numpy(lam), v, torch.from_numpy(it.astype(np.int64)), out)
 
     def last_round_sums(self):
         """Row sums s_0 .. s_{rounds-1} of the last ``solve(trace_sums=True)``

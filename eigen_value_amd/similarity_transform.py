@@ -112,6 +112,33 @@ class EigenValue:
         _lib.check(ts, "max_eigen_value_ex", self.so_lib)
         return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0]), stats.as_dict()
 
+    # ------------------------------------------------------------------
+    def similarity_transform_batched(self, mats: np.ndarray, *, eps: Optional[float] = None,
+                                     max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL):
+        """Many small matrices in one launch (``max_eigen_value_batched_ex``):
+        ``mats`` is a float32 or float64 array of shape ``(B, n, n)``, n up to
+        ``st_solve_batched_max_dim`` (256 / 128).  Every matrix is solved
+        exactly as ``similarity_transform`` would solve it alone, by its own
+        workgroup.
+
+        Returns ``(λ[B], v[B, n], ts_ms, iterations[B])``: numpy arrays of the
+        input dtype (``uint32`` for the counts)."""
+        assert mats.ndim == 3, "must be a (B, n, n) batch of square matrices !"
+        b, m, n = mats.shape
+        assert m == n, "must be square matrices of floating points !"
+        assert mats.dtype.num in (11, 12), "dtype of input matrices must be float32 or float64 !"
+        mats = np.ascontiguousarray(mats)
+        eigen_vals = np.empty(b, dtype=mats.dtype)
+        eigen_vecs = np.empty((b, n), dtype=mats.dtype)
+        iter_cnts = np.zeros(b, dtype=np.uint32)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics, 0, 0)
+        dtype = _lib.DTYPE_F32 if mats.dtype == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_batched_ex(
+            self.sycl_q, dtype, mats.ctypes.data, eigen_vals.ctypes.data,
+            eigen_vecs.ctypes.data, b, n, iter_cnts.ctypes.data, ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_batched_ex", self.so_lib)
+        return eigen_vals, eigen_vecs, int(ts), iter_cnts
+
     def last_round_times(self) -> np.ndarray:
         """Per-round kernel times (ms) of the last ``similarity_transform_ex``
         call made with ``time_kernels=True`` (empty otherwise)."""

@@ -175,6 +175,53 @@ int64_t st_solve_device_f64(void* wq, double* d_mat, unsigned int dim,
                             const st_options* opt, st_stats* stats);
 
 /* ---------------------------------------------------------------------- */
+/* 3a. batched solve (many small matrices, one launch)                     */
+/* ---------------------------------------------------------------------- */
+
+/* `batch` independent solves of dim x dim matrices in ONE launch, a
+ * workgroup per matrix (k_solve_batched): dim from 1 to
+ * st_solve_batched_max_dim (the matrix stays in one workgroup's registers).
+ * d_mats: device pointer [batch][dim][dim], contiguous, row-major; every
+ * matrix is TRANSFORMED IN PLACE like st_solve_device_*'s and ends at its
+ * own A_end.  For dim % (16 / sizeof(element)) == 0 and a 16-byte aligned
+ * d_mats every entry's eigen_val, eigenvector, iter_cnt, converged flag and
+ * final matrix are bit-identical to st_solve_device_* on that matrix alone;
+ * other dims sum a row in the same lane layout (the single solve sums them
+ * element-wide), so they agree to rounding.  d_eigen_vecs: device pointer
+ * [batch][dim] or NULL (then eigen_vecs_host must be non-NULL and receives
+ * them; both may be given).  eigen_vals, iter_cnts, converged (1 where the
+ * stop test passed before max_itr; may be NULL): host pointers [batch].
+ * opt->eps, max_itr and semantics as in st_solve_device_*; opt->batch is
+ * ignored; ST_FLAG_MATRIX_FREE, ST_FLAG_TIME_KERNELS, ST_FLAG_TRACE_SUMS
+ * and ST_FLAG_ROUND_LOOP are errors, as are dim == 0, dim above the limit
+ * and batch > 2^31 - 1 (never a fallback to another path).  batch == 0 is a
+ * no-op returning 0.  stats->rounds is the largest number of rounds any
+ * matrix evaluated, stats->converged 1 only if every matrix converged.
+ * Returns loop ms or negative. */
+int64_t st_solve_batched_f32(void* wq, float* d_mats, unsigned int batch,
+                             unsigned int dim, float* d_eigen_vecs,
+                             float* eigen_vecs_host, float* eigen_vals,
+                             unsigned int* iter_cnts, unsigned int* converged,
+                             const st_options* opt, st_stats* stats);
+int64_t st_solve_batched_f64(void* wq, double* d_mats, unsigned int batch,
+                             unsigned int dim, double* d_eigen_vecs,
+                             double* eigen_vecs_host, double* eigen_vals,
+                             unsigned int* iter_cnts, unsigned int* converged,
+                             const st_options* opt, st_stats* stats);
+/* The host-pointer twin (copies in, solves, copies out; mats is read only).
+ * dtype: 0 = float32, 1 = float64.  mats [batch][dim][dim], eigen_vals
+ * [batch], eigen_vecs [batch][dim], iter_cnts [batch]: host pointers.
+ * Returns h2d + loop ms or negative. */
+int64_t max_eigen_value_batched_ex(void* wq, int dtype, const void* mats,
+                                   void* eigen_vals, void* eigen_vecs,
+                                   unsigned int batch, unsigned int dim,
+                                   unsigned int* iter_cnts,
+                                   const st_options* opt, st_stats* stats);
+/* Largest dim the batched solve accepts for dtype (0 = f32: 256,
+ * 1 = f64: 128; anything else: 0).  No GPU needed. */
+unsigned int st_solve_batched_max_dim(int dtype);
+
+/* ---------------------------------------------------------------------- */
 /* 3b. native multi-GPU solve (one process, ngpus devices, RCCL)           */
 /* ---------------------------------------------------------------------- */
 

@@ -22,7 +22,9 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # only they name is evidence nothing relies on)
 SOURCES = ["DESIGN.md", "README.md", "INTEGRATION.md", "bench.py", "tests/*.py",
            "eigen_value_amd/*.py", "eigen_value_amd/csrc/*", "include/*.h"]
-TOKEN = re.compile(r"r0\d_[A-Za-z0-9_*{},.\-\[\]]+")
+# a round-numbered name anywhere (`r06_k0_probe.log`), or any name written
+# with its directory (`profiles/batched_solve.json`)
+TOKEN = re.compile(r"r0\d_[A-Za-z0-9_*{},.\-\[\]]+|(?<=profiles/)[A-Za-z][A-Za-z0-9_*{},.\-\[\]]+")
 
 
 def braces(p):
