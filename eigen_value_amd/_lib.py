@@ -26,6 +26,7 @@ ST_FLAG_MATRIX_FREE = 2
 ST_FLAG_ROUND_LOOP = 4
 ST_FLAG_WRITE_EVERY_ROUND = 8
 ST_FLAG_TRACE_SUMS = 16
+ST_FLAG_BATCH_ROUNDS = 32
 ST_MAX_ITR = 1000
 
 DTYPE_F32 = 0
@@ -198,6 +199,8 @@ def _declare(L: ctypes.CDLL) -> None:
     L.max_eigen_value_batched_ex.restype = i64
     L.st_solve_batched_max_dim.argtypes = [i32]
     L.st_solve_batched_max_dim.restype = u32
+    L.st_solve_batched_rounds_max_dim.argtypes = [i32]
+    L.st_solve_batched_rounds_max_dim.restype = u32
     L.st_last_round_times.argtypes = [P, P, u32]
     L.st_last_round_times.restype = i32
     L.st_last_round_sums.argtypes = [P, P, u32]
@@ -279,6 +282,21 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_launch_policy_query.restype = i32
     L.st_state_reset.argtypes = [P, P]
     L.st_state_reset.restype = i32
+
+
+def batch_rounds_flag(round_loop, n: int, dtype_code: int) -> int:
+    """The ``round_loop`` keyword of the batched solves as option flags:
+    ``None`` / ``False`` 0 (the one-launch kernel), ``True``
+    ST_FLAG_BATCH_ROUNDS, ``"auto"`` the flag only where n is beyond the
+    one-launch kernel (st_solve_batched_max_dim).  Anything else is a
+    ValueError, raised before any library call."""
+    if round_loop is None or round_loop is False:
+        return 0
+    if round_loop is True:
+        return ST_FLAG_BATCH_ROUNDS
+    if isinstance(round_loop, str) and round_loop == "auto":
+        return ST_FLAG_BATCH_ROUNDS if n > load().st_solve_batched_max_dim(dtype_code) else 0
+    raise ValueError(f'round_loop must be None, True or "auto", got {round_loop!r}')
 
 
 def round_sums(L: ctypes.CDLL, q, n: int, dtype):

@@ -718,6 +718,51 @@ k_round(T* a, const T* __restrict__ s_cur, T* __restrict__ s_next,
 }
 
 // ---------------------------------------------------------------------------
+// round k of every matrix of a contiguous [batch][ncols][ncols] array in one
+// launch (solve_batched_rounds in st_solve.hip): blockIdx.y / .z select the
+// matrix b, its s_cur / s_next / v slices and its own st_state; blockIdx.x /
+// gridDim.x are the matrix's row-group walk exactly as in k_round.  The body
+// is k_round's (round_body, same template arguments for the same n), so every
+// matrix gets the bits of a k_round launch on it alone; a matrix that has
+// stopped (state[b].end <= k) costs workgroups that return at once.
+// `finished` counts the matrices whose recorded round set end: the thread
+// that recorded round k (workgroup x = 0, thread 0) adds 1 when its matrix
+// ends in this round, so the host reads one word per check instead of
+// `batch` states (k_count_mirror).
+// ---------------------------------------------------------------------------
+template <typename T, int ROWS, int W, int U, int ORDER, int NT,
+          int BLK = kBlock, bool ALT = false>
+__global__ __launch_bounds__(BLK) void
+k_round_batched(T* a, const T* s_cur, T* s_next, T* v, uint32_t ng_main,
+                uint32_t nrem, uint32_t ncols, T eps, uint32_t k,
+                uint32_t max_itr, uint32_t semantics, st_state* state,
+                uint32_t batch, uint32_t* finished)
+{
+  const uint32_t b = blockIdx.z * gridDim.y + blockIdx.y;
+  if (b >= batch)
+    return;
+  const size_t off = (size_t)b * ncols;
+  st_state* const st_b = state + b;
+  round_body<T, ROWS, W, U, ORDER, NT, BLK, ALT, kSpanFull>(
+    a + off * ncols, s_cur + off, s_next + off, v + off, ng_main, nrem, ncols,
+    0u, eps, k, max_itr, semantics, st_b, nullptr, 0u, 0u);
+  // (a gated launch reads end <= k here and counts nothing)
+  if (blockIdx.x == 0 && threadIdx.x == 0 && st_b->end == k + 1)
+    atomicAdd(finished, 1u);
+}
+
+// The batched round loop's per-batch look at the finished counter: one lane
+// copies it to the caller's pinned, host-coherent word with a system-scope
+// vector store, in stream order behind the batch's rounds (k_state_mirror's
+// way).
+__global__ __launch_bounds__(64) void
+k_count_mirror(const uint32_t* __restrict__ d, uint32_t* h)
+{
+  if (threadIdx.x == 0)
+    __hip_atomic_store(h, *d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---------------------------------------------------------------------------
 // the round split in two launches, for a sharded solve whose all-gather of
 // s_k overlaps the first (sharded.py, overlap=True).  Rank p owns rows
 // [row0, row0 + nrows) and therefore computed s_k for exactly the matching

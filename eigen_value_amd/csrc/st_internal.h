@@ -75,6 +75,18 @@ int launch_round(T* a, const T* s_cur, T* s_next, T* v, uint32_t nrows,
                  uint32_t ncols, uint32_t row0, T eps, uint32_t k,
                  uint32_t max_itr, uint32_t semantics, st_state* st,
                  hipStream_t stream);
+// round k of every matrix of a contiguous [batch][n][n] array in one launch
+// (k_round_batched; n below the flat threshold): s_cur / s_next / v are
+// [batch][n], st [batch]; each matrix runs launch_round's instantiation for
+// n x n and adds 1 to *finished in the round that ends it
+template <typename T>
+int launch_round_batched(T* a, const T* s_cur, T* s_next, T* v, uint32_t batch,
+                         uint32_t n, T eps, uint32_t k, uint32_t max_itr,
+                         uint32_t semantics, st_state* st, uint32_t* finished,
+                         hipStream_t stream);
+// the finished counter -> a pinned host-coherent word, in stream order
+int launch_count_mirror(const uint32_t* d_count, uint32_t* h_count,
+                        hipStream_t stream);
 // the flat round for large blocks (k_flat + k_parts); `part`
 // holds round_flat_scratch(nrows, ncols) elements
 template <typename T>

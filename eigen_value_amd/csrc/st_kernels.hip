@@ -50,11 +50,15 @@
 #ifndef ST_FLAT_ALT // the flat launches' odd-round order (2 = reversed per XCD, 0 = none)
 #define ST_FLAT_ALT 2
 #endif
+#ifndef ST_BATCHED_ROUND_WGS // workgroups a batched round launch aims at in total
+#define ST_BATCHED_ROUND_WGS 2048u
+#endif
 #define ST_PROBES_DEFAULT                                                      \
   (ST_DPP_NOINIT == 1 && ST_ROW_VLOAD == 0 && ST_FLAT_UNMASKED == 1 &&         \
    ST_DEFER_STORE_NT == 0 && ST_EVERY_CACHED_R1 == 1 &&                        \
    ST_DEFER_R0_CACHED == 1 && ST_DEFER_PT0_CACHED == 4 &&                      \
-   ST_DEFER_STORE_R8_CACHED == 1 && ST_DEFER_TS5_CACHED == 16 && ST_FLAT_ALT == 2)
+   ST_DEFER_STORE_R8_CACHED == 1 && ST_DEFER_TS5_CACHED == 16 && ST_FLAT_ALT == 2 && \
+   ST_BATCHED_ROUND_WGS == 2048)
 #ifndef ST_PROBES
 static_assert(ST_PROBES_DEFAULT,
               "A/B probe switch set in a library build (use -DST_PROBES=1)");
@@ -464,18 +468,20 @@ launch_round_cfg(T* a, const T* s_cur, T* s_next, T* v, uint32_t nrows,
     eps, k, max_itr, semantics, st);
 }
 
-template <typename T, int W, int ORDER>
+// The every-round kernel's template arguments for an nrows x ncols block at
+// `a` with row sums at `s_cur`: go(W, ORDER, ROWS, NT) as integral constants,
+// and round_shape's workgroup cap.  launch_round (k_round) and
+// launch_round_batched (k_round_batched) both choose through this, so a
+// matrix of a batch runs the instantiation its single solve runs.
+template <typename T, int W, int ORDER, typename F>
 void
-launch_round_rows(T* a, const T* s_cur, T* s_next, T* v, uint32_t nrows,
-                  uint32_t ncols, uint32_t row0, T eps, uint32_t k,
-                  uint32_t max_itr, uint32_t semantics, st_state* st,
-                  hipStream_t stream)
+round_dispatch_rows(uint32_t nrows, uint32_t ncols, F&& go)
 {
+  using std::integral_constant;
   const Shape sh = round_shape(nrows, ncols, sizeof(T));
 #define ST_ROUND_CFG(R, N)                                                     \
-  launch_round_cfg<T, R, W, ORDER, N>(a, s_cur, s_next, v, nrows, ncols, row0, \
-                                      eps, k, max_itr, semantics, st, sh.grid, \
-                                      stream)
+  go(integral_constant<int, W>{}, integral_constant<int, ORDER>{},            \
+     integral_constant<int, R>{}, integral_constant<int, N>{}, sh.grid)
   using dev::kCached;
   using dev::kNtBoth;
   if (sh.rows == 1)
@@ -485,6 +491,27 @@ launch_round_rows(T* a, const T* s_cur, T* s_next, T* v, uint32_t nrows,
   else
     sh.nt ? ST_ROUND_CFG(4, kNtBoth) : ST_ROUND_CFG(4, kCached);
 #undef ST_ROUND_CFG
+}
+
+template <typename T, typename F>
+void
+round_dispatch(const T* a, const T* s_cur, uint32_t nrows, uint32_t ncols,
+               uint32_t semantics, F&& go)
+{
+  constexpr int W = 16 / sizeof(T);
+  const bool vec_ok = (ncols % W) == 0 && aligned16(a) && aligned16(s_cur);
+  const bool order1 = semantics == ST_SEM_MAINPY;
+  if (vec_ok) {
+    if (order1)
+      round_dispatch_rows<T, W, 1>(nrows, ncols, go);
+    else
+      round_dispatch_rows<T, W, 0>(nrows, ncols, go);
+  } else {
+    if (order1)
+      round_dispatch_rows<T, 1, 1>(nrows, ncols, go);
+    else
+      round_dispatch_rows<T, 1, 0>(nrows, ncols, go);
+  }
 }
 
 template <typename T, int ROWS, int W, int ORDER, int NT, int SPAN>
@@ -709,26 +736,139 @@ launch_round(T* a, const T* s_cur, T* s_next, T* v, uint32_t nrows,
   // every launch must own >= 1 row: the stop test and m_k are derived from
   // the sweep of a row group (the sharded driver rejects empty row blocks)
   ST_REQUIRE(nrows > 0, "round: nrows must be > 0");
-  constexpr int W = 16 / sizeof(T);
-  const bool vec_ok = (ncols % W) == 0 && aligned16(a) && aligned16(s_cur);
-  const bool order1 = semantics == ST_SEM_MAINPY;
-  if (vec_ok) {
-    if (order1)
-      launch_round_rows<T, W, 1>(a, s_cur, s_next, v, nrows, ncols, row0, eps,
-                                 k, max_itr, semantics, st, stream);
-    else
-      launch_round_rows<T, W, 0>(a, s_cur, s_next, v, nrows, ncols, row0, eps,
-                                 k, max_itr, semantics, st, stream);
-  } else {
-    if (order1)
-      launch_round_rows<T, 1, 1>(a, s_cur, s_next, v, nrows, ncols, row0, eps,
-                                 k, max_itr, semantics, st, stream);
-    else
-      launch_round_rows<T, 1, 0>(a, s_cur, s_next, v, nrows, ncols, row0, eps,
-                                 k, max_itr, semantics, st, stream);
-  }
+  round_dispatch<T>(a, s_cur, nrows, ncols, semantics,
+                    [&](auto w, auto order, auto rows, auto nt, uint32_t cap) {
+                      launch_round_cfg<T, decltype(rows)::value, decltype(w)::value,
+                                       decltype(order)::value, decltype(nt)::value>(
+                        a, s_cur, s_next, v, nrows, ncols, row0, eps, k, max_itr,
+                        semantics, st, cap, stream);
+                    });
   return check_launch("round");
 }
+
+// workgroups a batched round launch aims at in total (the per-matrix grid is
+// this over the batch, within [1, min(row groups, round_shape's cap)]):
+// 8 per CU, the most 256-thread workgroups a CU holds (DESIGN.md §Batched
+// solve has the A/B; probe switch ST_BATCHED_ROUND_WGS)
+namespace {
+constexpr uint32_t kBatchedRoundWgs = ST_BATCHED_ROUND_WGS;
+// total batch bytes from which a batched round's matrix accesses are
+// non-temporal (profiles/batched_rounds_nt.json, ms per call, cached vs
+// non-temporal: 256 x 2048^2 fp64, 8 GiB, 15.30 vs 14.35; 256 x 1024^2,
+// 2 GiB, 3.93 vs 3.73; 64 x 2048^2, 2 GiB, 3.85 vs 3.79; below that it
+// loses: 256 x 512^2, 512 MiB, 1.04 vs 1.10; 64 x 512^2 0.324 vs 0.367)
+constexpr size_t kBatchedRoundNtBytes = (size_t)2 << 30;
+
+// the grid's y / z limits of the current device (queried once per device)
+int
+grid_yz_limits(uint32_t* ymax, uint32_t* zmax)
+{
+  constexpr int kMaxDev = 64;
+  static std::atomic<uint32_t> cache[kMaxDev][2];
+  int dev = 0;
+  ST_CHECK(hipGetDevice(&dev));
+  const bool cached = dev >= 0 && dev < kMaxDev;
+  if (cached && cache[dev][0].load(std::memory_order_acquire) != 0) {
+    *ymax = cache[dev][0].load(std::memory_order_relaxed);
+    *zmax = cache[dev][1].load(std::memory_order_relaxed);
+    return 0;
+  }
+  int y = 0, z = 0;
+  ST_CHECK(hipDeviceGetAttribute(&y, hipDeviceAttributeMaxGridDimY, dev));
+  ST_CHECK(hipDeviceGetAttribute(&z, hipDeviceAttributeMaxGridDimZ, dev));
+  ST_REQUIRE(y > 0 && z > 0, "round_batched: grid limits %d x %d", y, z);
+  *ymax = (uint32_t)y;
+  *zmax = (uint32_t)z;
+  if (cached) {
+    cache[dev][1].store(*zmax, std::memory_order_relaxed);
+    cache[dev][0].store(*ymax, std::memory_order_release);
+  }
+  return 0;
+}
+} // namespace
+
+// Round k of every matrix of the contiguous [batch][n][n] array `a` in one
+// launch (k_round_batched): matrix b's row sums at s_cur / s_next + b n, its
+// v at v + b n, its state at st + b; *finished counts the matrices that end.
+// The template arguments are launch_round's for an n x n matrix at `a` (every
+// matrix of the batch shares n, and for n % W == 0 the alignment of `a` and
+// `s_cur`; otherwise all take the element-wide path).  blockIdx.y / .z carry
+// the matrix index; a batch beyond ymax * zmax goes in several launches.
+template <typename T>
+int
+launch_round_batched(T* a, const T* s_cur, T* s_next, T* v, uint32_t batch,
+                     uint32_t n, T eps, uint32_t k, uint32_t max_itr,
+                     uint32_t semantics, st_state* st, uint32_t* finished,
+                     hipStream_t stream)
+{
+  ST_REQUIRE(a && s_cur && s_next && v && st && finished,
+             "round_batched: null pointer");
+  ST_REQUIRE(n > 0, "round_batched: n must be > 0");
+  ST_REQUIRE(!flat_round_pays(n, n, sizeof(T)),
+             "round_batched: n = %u takes the flat round", n);
+  ST_REQUIRE(semantics <= ST_SEM_MAINPY, "round_batched: bad semantics %u",
+             semantics);
+  ST_REQUIRE(max_itr > 0, "round_batched: max_itr must be > 0");
+  if (batch == 0)
+    return 0;
+  uint32_t ymax = 0, zmax = 0;
+  if (grid_yz_limits(&ymax, &zmax))
+    return -1;
+  const uint64_t per_launch = (uint64_t)ymax * zmax;
+  const uint32_t target = kBatchedRoundWgs;
+  round_dispatch<T>(
+    a, s_cur, n, n, semantics,
+    [&](auto w, auto order, auto rows, auto nt, uint32_t cap) {
+      constexpr int R = decltype(rows)::value, W = decltype(w)::value;
+      const uint32_t ng_main = n / R, nrem = n % R;
+      const uint32_t ng = ng_main + nrem;
+      const uint32_t most = ng < cap ? ng : cap;
+      auto launch = [&](auto ntc) {
+        for (uint64_t b0 = 0; b0 < batch; b0 += per_launch) {
+          const uint32_t nb =
+            (uint32_t)(batch - b0 < per_launch ? batch - b0 : per_launch);
+          uint32_t gx = target / batch; // per matrix, of the whole batch
+          gx = gx < 1 ? 1 : (gx > most ? most : gx);
+          const uint32_t gz = (nb + ymax - 1) / ymax;
+          const uint32_t gy = (nb + gz - 1) / gz; // gy * gz >= nb, padding < gz
+          const size_t off = (size_t)b0 * n;
+          hipLaunchKernelGGL(
+            (dev::k_round_batched<T, R, W, kChunks<T, W, kUnroll>,
+                                  decltype(order)::value, decltype(ntc)::value,
+                                  kBlock, true>),
+            dim3(gx, gy, gz), dim3(kBlock), 0, stream, a + off * n,
+            s_cur + off, s_next + off, v + off, ng_main, nrem, n, eps, k,
+            max_itr, semantics, st + b0, nb, finished);
+        }
+      };
+      // the cache policy goes by the bytes the launch streams, the whole
+      // batch's: non-temporal from 2 GiB (it does not change any value)
+      if (block_bytes(n, n, sizeof(T)) * batch >= kBatchedRoundNtBytes)
+        launch(std::integral_constant<int, dev::kNtBoth>{});
+      else
+        launch(nt);
+    });
+  return check_launch("round_batched");
+}
+
+int
+launch_count_mirror(const uint32_t* d_count, uint32_t* h_count,
+                    hipStream_t stream)
+{
+  ST_REQUIRE(d_count && h_count, "count_mirror: null pointer");
+  hipLaunchKernelGGL(dev::k_count_mirror, dim3(1), dim3(64), 0, stream, d_count,
+                     h_count);
+  return check_launch("count_mirror");
+}
+
+template int launch_round_batched<float>(float*, const float*, float*, float*,
+                                         uint32_t, uint32_t, float, uint32_t,
+                                         uint32_t, uint32_t, st_state*,
+                                         uint32_t*, hipStream_t);
+template int launch_round_batched<double>(double*, const double*, double*,
+                                          double*, uint32_t, uint32_t, double,
+                                          uint32_t, uint32_t, uint32_t,
+                                          st_state*, uint32_t*, hipStream_t);
 
 template <typename T>
 int
@@ -1980,7 +2120,8 @@ st_probe_switches(void)
                      " ST_DEFER_PT0_CACHED=" ST_STR(ST_DEFER_PT0_CACHED)
                        " ST_DEFER_STORE_R8_CACHED=" ST_STR(
                          ST_DEFER_STORE_R8_CACHED) " ST_DEFER_TS5_CACHED=" ST_STR(
-                           ST_DEFER_TS5_CACHED) " ST_FLAT_ALT=" ST_STR(ST_FLAT_ALT);
+                           ST_DEFER_TS5_CACHED) " ST_FLAT_ALT=" ST_STR(ST_FLAT_ALT)
+                             " ST_BATCHED_ROUND_WGS=" ST_STR(ST_BATCHED_ROUND_WGS);
 }
 
 unsigned int

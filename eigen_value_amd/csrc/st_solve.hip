@@ -16,6 +16,9 @@
 //     derives m_k/stop_k from its own sweep of s_k; workgroup 0 records)
 //     A_{k+1} = D_k^-1 A_k D_k in place, s_{k+1} = rowsum(A_{k+1})
 //     (launches after the stop round return at once)
+// A batch of matrices runs k_solve_batched (one launch, a workgroup per
+// matrix) or, with ST_FLAG_BATCH_ROUNDS, this loop with every launch
+// covering the whole batch (k_round_batched, solve_batched_rounds).
 // The reference blocks on a host_accessor every round
 // (similarity_transform.cpp:45-50).  Here rounds are enqueued in batches;
 // the host checks the device `done` flag of batch b while batch b+1 is
@@ -88,6 +91,12 @@ struct Context
   st_state* d_bstate = nullptr;
   size_t bstate_cap = 0; // states
   std::vector<st_state> h_bstate;
+  // batched round loop: [s0 | s1 | v], each bsum_bytes ([batch][n]); the
+  // count of finished matrices and its pinned host mirror (2 slots)
+  void* d_bsum = nullptr;
+  size_t bsum_bytes = 0;
+  uint32_t* d_bcount = nullptr;
+  uint32_t* h_bcount = nullptr;
 };
 
 double
@@ -187,6 +196,44 @@ ensure_bstate(Context* c, size_t count)
   ST_CHECK(hipMalloc((void**)&c->d_bstate, count * sizeof(st_state)));
   c->bstate_cap = count;
   return 0;
+}
+
+int
+ensure_bsum(Context* c, size_t bytes)
+{
+  bytes = (bytes + 255) & ~(size_t)255;
+  if (!c->d_bcount)
+    ST_CHECK(hipMalloc((void**)&c->d_bcount, sizeof(uint32_t)));
+  if (!c->h_bcount)
+    ST_CHECK(hipHostMalloc((void**)&c->h_bcount, 2 * sizeof(uint32_t),
+                           hipHostMallocCoherent | hipHostMallocMapped));
+  if (c->d_bsum && c->bsum_bytes >= bytes)
+    return 0;
+  if (c->d_bsum) {
+    ST_CHECK(hipStreamSynchronize(c->stream));
+    ST_CHECK(hipFree(c->d_bsum));
+    c->d_bsum = nullptr;
+    c->bsum_bytes = 0;
+  }
+  ST_CHECK(hipMalloc(&c->d_bsum, 3 * bytes));
+  c->bsum_bytes = bytes;
+  return 0;
+}
+
+// the largest n whose single solve takes the k_round path: the last n below
+// the flat threshold (round_flat_pays is monotone in n)
+uint32_t
+batched_rounds_max_n(size_t elem)
+{
+  uint32_t lo = 0, hi = 1u << 20; // pays(hi), !pays(lo)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (round_flat_pays(mid, mid, elem))
+      hi = mid;
+    else
+      lo = mid;
+  }
+  return lo;
 }
 
 template <typename T>
@@ -519,12 +566,111 @@ batched_args(Context* c, uint32_t batch, uint32_t n, const st_options* opt,
              "ST_FLAG_TRACE_SUMS and ST_FLAG_ROUND_LOOP are not supported "
              "(flags = %u)", o->flags);
   ST_REQUIRE(n > 0, "dim must be > 0");
-  ST_REQUIRE(n <= solve_batched_max_n<T>(),
-             "batched solve: dim = %u exceeds the one-workgroup limit %u "
-             "(st_solve_batched_max_dim)", n, solve_batched_max_n<T>());
+  if (o->flags & ST_FLAG_BATCH_ROUNDS)
+    ST_REQUIRE(n <= batched_rounds_max_n(sizeof(T)),
+               "batched solve: dim = %u exceeds the round-loop limit %u "
+               "(st_solve_batched_rounds_max_dim)", n,
+               batched_rounds_max_n(sizeof(T)));
+  else
+    ST_REQUIRE(n <= solve_batched_max_n<T>(),
+               "batched solve: dim = %u exceeds the one-workgroup limit %u "
+               "(st_solve_batched_max_dim)", n, solve_batched_max_n<T>());
   ST_REQUIRE(batch <= 0x7fffffffu,
              "batched solve: batch = %u exceeds the grid limit 2^31 - 1", batch);
   return 0;
+}
+
+// The batched solve for matrices beyond one workgroup's registers
+// (ST_FLAG_BATCH_ROUNDS): solve_device's round loop with every launch
+// covering the whole batch (k_round_batched, blockIdx.y / .z = the matrix).
+// Once per call: one memset of the states and the finished counter, one fill
+// of v, one K0 pass over the batch seen as a tall (batch n) x n matrix (a
+// row's sum does not depend on the rows around it).  Per host check
+// (opt->batch rounds, default 8) one word, the count of finished matrices,
+// is mirrored to pinned memory; the loop stops enqueuing once it reaches
+// `batch`.  The caller (solve_batched) has checked the arguments.
+template <typename T>
+int64_t
+solve_batched_rounds(Context* c, T* d_mats, uint32_t batch, uint32_t n,
+                     T* d_v_out, T* v_host, T* eigen_vals, uint32_t* iter_cnts,
+                     uint32_t* converged, const Resolved& o, st_stats* stats)
+{
+  const size_t v_bytes = sizeof(T) * (size_t)batch * n;
+  if (ensure_device(c) || ensure_bstate(c, batch) || ensure_bsum(c, v_bytes))
+    return -1;
+  T* s_buf[2] = { reinterpret_cast<T*>(c->d_bsum),
+                  reinterpret_cast<T*>((char*)c->d_bsum + c->bsum_bytes) };
+  T* d_v = d_v_out ? d_v_out
+                   : reinterpret_cast<T*>((char*)c->d_bsum + 2 * c->bsum_bytes);
+  hipStream_t s = c->stream;
+  const uint32_t per_check = o.batch ? o.batch : kDefaultBatch;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)batch, s));
+  ST_CHECK(hipMemsetAsync(c->d_bcount, 0, sizeof(uint32_t), s));
+  if (launch_fill<T>(d_v, (uint64_t)batch * n, (T)1, s))
+    return -1;
+  // K0, in passes of whole matrices whose rows fit the launcher's uint32_t
+  const uint32_t per_pass = 0x7fffffffu / n;
+  for (uint32_t b0 = 0; b0 < batch; b0 += per_pass) {
+    const uint32_t nb = batch - b0 < per_pass ? batch - b0 : per_pass;
+    if (launch_rowsum<T>(d_mats + (size_t)b0 * n * n, s_buf[0] + (size_t)b0 * n,
+                         nb * n, n, s))
+      return -1;
+  }
+  const T eps = (T)o.eps;
+  uint32_t enqueued = 0, cur = 0, batch_no = 0;
+  bool done = false;
+  while (!done && enqueued < o.max_itr) {
+    const uint32_t b = (o.max_itr - enqueued) < per_check ? (o.max_itr - enqueued)
+                                                          : per_check;
+    for (uint32_t j = 0; j < b; j++) {
+      if (launch_round_batched<T>(d_mats, s_buf[cur], s_buf[cur ^ 1], d_v, batch,
+                                  n, eps, enqueued + j, o.max_itr, o.semantics,
+                                  c->d_bstate, c->d_bcount, s))
+        return -1;
+      cur ^= 1;
+    }
+    enqueued += b;
+    const int slot = batch_no & 1;
+    if (launch_count_mirror(c->d_bcount, &c->h_bcount[slot], s))
+      return -1;
+    ST_CHECK(hipEventRecord(c->ev_flag[slot], s));
+    // wait for the previous batch's count while this batch runs
+    if (batch_no > 0) {
+      ST_CHECK(hipEventSynchronize(c->ev_flag[slot ^ 1]));
+      done = c->h_bcount[slot ^ 1] >= batch;
+    }
+    batch_no++;
+  }
+  ST_CHECK(hipStreamSynchronize(s));
+  c->h_bstate.resize(batch);
+  ST_CHECK(hipMemcpy(c->h_bstate.data(), c->d_bstate,
+                     sizeof(st_state) * (size_t)batch, hipMemcpyDeviceToHost));
+  const double loop_ms = ms_since(t0);
+
+  const auto t1 = std::chrono::steady_clock::now();
+  uint32_t rounds = 0, all = 1;
+  for (uint32_t b = 0; b < batch; b++) {
+    const st_state& fin = c->h_bstate[b];
+    ST_REQUIRE(fin.done, "internal: matrix %u ended without done flag", b);
+    eigen_vals[b] = (T)fin.lambda;
+    iter_cnts[b] = fin.iters;
+    if (converged)
+      converged[b] = fin.stop;
+    rounds = fin.end > rounds ? fin.end : rounds;
+    all &= fin.stop;
+  }
+  if (v_host)
+    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
+  const double d2h_ms = ms_since(t1);
+  if (stats) {
+    stats->loop_ms = loop_ms;
+    stats->d2h_ms = d2h_ms;
+    stats->rounds = rounds;
+    stats->converged = all;
+    stats->fused_launches = enqueued;
+  }
+  return (int64_t)loop_ms;
 }
 
 // Many small solves in one launch (k_solve_batched: a workgroup per matrix
@@ -549,6 +695,9 @@ solve_batched(Context* c, T* d_mats, uint32_t batch, uint32_t n, T* d_v_out,
   ST_REQUIRE(d_mats, "null matrix");
   ST_REQUIRE(eigen_vals && iter_cnts, "null output pointer");
   ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
+  if (o.flags & ST_FLAG_BATCH_ROUNDS) // one launch per round for the batch
+    return solve_batched_rounds<T>(c, d_mats, batch, n, d_v_out, v_host,
+                                   eigen_vals, iter_cnts, converged, o, stats);
   const size_t v_bytes = sizeof(T) * (size_t)batch * n;
   if (ensure_device(c) || ensure_bstate(c, batch) ||
       (!d_v_out && ensure_part(c, v_bytes))) // d_part: free outside flat rounds
@@ -728,6 +877,12 @@ destroy_queue(void* wq)
     (void)hipFree(c->d_state);
   if (c->d_bstate)
     (void)hipFree(c->d_bstate);
+  if (c->d_bsum)
+    (void)hipFree(c->d_bsum);
+  if (c->d_bcount)
+    (void)hipFree(c->d_bcount);
+  if (c->h_bcount)
+    (void)hipHostFree(c->h_bcount);
   if (c->h_state)
     (void)hipHostFree(c->h_state);
   for (hipEvent_t e : c->ev_flag)
@@ -908,6 +1063,14 @@ st_solve_batched_max_dim(int dtype)
 {
   return dtype == 0   ? st::solve_batched_max_n<float>()
          : dtype == 1 ? st::solve_batched_max_n<double>()
+                      : 0u;
+}
+
+unsigned int
+st_solve_batched_rounds_max_dim(int dtype)
+{
+  return dtype == 0   ? st::batched_rounds_max_n(sizeof(float))
+         : dtype == 1 ? st::batched_rounds_max_n(sizeof(double))
                       : 0u;
 }
 

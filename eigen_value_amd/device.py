@@ -355,6 +355,16 @@ def batched_max_dim(dtype) -> int:
     return int(_lib.load().st_solve_batched_max_dim(1 if name == "float64" else 0))
 
 
+def batched_rounds_max_dim(dtype) -> int:
+    """Largest n ``DeviceSolver.solve_batched(..., round_loop=True)`` accepts
+    for ``dtype`` (torch or numpy float32 / float64): 6143 / 4344, the sizes
+    below the 144 MiB flat threshold (st_solve_batched_rounds_max_dim)."""
+    name = str(dtype).split(".")[-1].strip("'>")
+    if name not in ("float32", "float64"):
+        raise TypeError(f"float32/float64 required, got {dtype}")
+    return int(_lib.load().st_solve_batched_rounds_max_dim(1 if name == "float64" else 0))
+
+
 
 class DeviceSolver:
     """Owns one library context bound to the current torch stream."""
@@ -428,10 +438,20 @@ class DeviceSolver:
         return float(ev.value), v, int(it.value), stats.as_dict()
 
     def solve_batched(self, mats, *, inplace: bool = False, eps: Optional[float] = None,
-                      max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL):
+                      max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
+                      round_loop=None, batch: int = 0):
         """Many small matrices in ONE launch, a workgroup per matrix
         (``st_solve_batched_*``).  ``mats``: a torch tensor or DLPack producer
         of shape (B, n, n) on this solver's device, n <= ``batched_max_dim``.
+
+        ``round_loop=True`` runs one launch per ROUND for the whole batch
+        instead (``ST_FLAG_BATCH_ROUNDS``, k_round_batched): any n up to
+        ``batched_rounds_max_dim`` (4344 fp64 / 6143 fp32), every entry
+        bit-identical to ``solve`` on that matrix alone at every n;
+        ``batch`` rounds are enqueued per host check (0 = 8) and
+        ``stats["fused_launches"]`` counts the rounds enqueued.
+        ``round_loop="auto"`` does so only where n > ``batched_max_dim``;
+        ``None`` is the one-launch kernel.
 
         Returns (λ: host tensor[B], v: device tensor[B, n], iterations: host
         tensor[B] (int64), stats: dict).  ``stats["converged_each"]`` is a
@@ -453,6 +473,7 @@ class DeviceSolver:
         assert mats.dim() == 3 and mats.shape[1] == mats.shape[2], "must be (B, n, n)"
         sfx = _sfx(mats)
         b, n = mats.shape[0], mats.shape[1]
+        flags = _lib.batch_rounds_flag(round_loop, n, 1 if sfx == "f64" else 0)
         if inplace and not mats.is_contiguous():
             raise ValueError("inplace needs a contiguous (B, n, n) tensor")
         work = (mats if inplace else mats.clone()).contiguous()
@@ -461,7 +482,8 @@ class DeviceSolver:
         lam = np.zeros(b, dtype=npdt)
         it = np.zeros(b, dtype=np.uint32)
         conv = np.zeros(b, dtype=np.uint32)
-        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics, 0, 0)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
         stats = _lib.st_stats()
         _lib.check(self.L.st_set_stream(self.q, _stream(mats.device)), "st_set_stream")
         rc = getattr(self.L, f"st_solve_batched_{sfx}")(

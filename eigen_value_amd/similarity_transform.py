@@ -114,12 +114,20 @@ class EigenValue:
 
     # ------------------------------------------------------------------
     def similarity_transform_batched(self, mats: np.ndarray, *, eps: Optional[float] = None,
-                                     max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL):
+                                     max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
+                                     round_loop=None):
         """Many small matrices in one launch (``max_eigen_value_batched_ex``):
         ``mats`` is a float32 or float64 array of shape ``(B, n, n)``, n up to
         ``st_solve_batched_max_dim`` (256 / 128).  Every matrix is solved
         exactly as ``similarity_transform`` would solve it alone, by its own
         workgroup.
+
+        ``round_loop=True`` takes one launch per round for the whole batch
+        instead (``ST_FLAG_BATCH_ROUNDS``): n up to
+        ``st_solve_batched_rounds_max_dim`` (6143 / 4344), results
+        bit-identical to per-matrix ``similarity_transform`` calls at every n.
+        ``round_loop="auto"`` does so only where n is beyond the one-launch
+        kernel; ``None`` is the one-launch kernel.
 
         Returns ``(λ[B], v[B, n], ts_ms, iterations[B])``: numpy arrays of the
         input dtype (``uint32`` for the counts)."""
@@ -127,12 +135,13 @@ class EigenValue:
         b, m, n = mats.shape
         assert m == n, "must be square matrices of floating points !"
         assert mats.dtype.num in (11, 12), "dtype of input matrices must be float32 or float64 !"
+        dtype = _lib.DTYPE_F32 if mats.dtype == np.float32 else _lib.DTYPE_F64
+        flags = _lib.batch_rounds_flag(round_loop, n, dtype)
         mats = np.ascontiguousarray(mats)
         eigen_vals = np.empty(b, dtype=mats.dtype)
         eigen_vecs = np.empty((b, n), dtype=mats.dtype)
         iter_cnts = np.zeros(b, dtype=np.uint32)
-        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics, 0, 0)
-        dtype = _lib.DTYPE_F32 if mats.dtype == np.float32 else _lib.DTYPE_F64
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics, 0, flags)
         ts = self.so_lib.max_eigen_value_batched_ex(
             self.sycl_q, dtype, mats.ctypes.data, eigen_vals.ctypes.data,
             eigen_vecs.ctypes.data, b, n, iter_cnts.ctypes.data, ctypes.byref(opt), None)

@@ -108,6 +108,10 @@ typedef struct st_options
 #define ST_FLAG_TRACE_SUMS 16u  /* record every evaluated round's row sums  */
                                 /* s_k (st_last_round_sums; max_itr * dim   */
                                 /* elements <= 1 GiB): identical results    */
+#define ST_FLAG_BATCH_ROUNDS 32u /* batched entry points only: one launch   */
+                                /* per round for the whole batch            */
+                                /* (k_round_batched), dim up to             */
+                                /* st_solve_batched_rounds_max_dim          */
 
 typedef struct st_stats
 {
@@ -220,6 +224,30 @@ int64_t max_eigen_value_batched_ex(void* wq, int dtype, const void* mats,
 /* Largest dim the batched solve accepts for dtype (0 = f32: 256,
  * 1 = f64: 128; anything else: 0).  No GPU needed. */
 unsigned int st_solve_batched_max_dim(int dtype);
+
+/* ST_FLAG_BATCH_ROUNDS in opt->flags of the three calls above selects the
+ * round-loop form of the batched solve, for matrices beyond one workgroup's
+ * registers: dim from 1 to st_solve_batched_rounds_max_dim, the sizes whose
+ * single solve runs one k_round launch per round (dim * dim elements below
+ * the 144 MiB flat threshold, st_round_flat_pays).  One launch per round
+ * covers the whole batch (k_round_batched: the grid's y / z select the
+ * matrix, its row sums, its eigenvector and its own state); a matrix that
+ * has stopped costs workgroups that return at once while the others carry
+ * on.  Rounds are enqueued opt->batch at a time (0 = 8) and the host looks
+ * at one word, the count of finished matrices, per check.  Every matrix is
+ * transformed in place to its own A_end.  For a 16-byte aligned d_mats every
+ * entry's eigen_val, eigenvector, iter_cnt, converged flag and final matrix
+ * are bit-identical to st_solve_device_* on that matrix alone AT EVERY DIM:
+ * each matrix runs the kernel instantiation of its single solve on the same
+ * lane layout (dims with dim % (16 / sizeof(element)) != 0 included: both
+ * sides take the element-wide path there).  stats->fused_launches is the
+ * number of rounds enqueued.  Without the flag the calls behave exactly as
+ * documented above.  ST_FLAG_MATRIX_FREE, ST_FLAG_TIME_KERNELS,
+ * ST_FLAG_TRACE_SUMS and ST_FLAG_ROUND_LOOP stay errors; a dim above the
+ * limit is an error ("exceeds the round-loop limit"), never a fallback. */
+/* Largest dim of the round-loop form for dtype (0 = f32: 6143, 1 = f64:
+ * 4344; anything else: 0), derived from st_round_flat_pays.  No GPU needed. */
+unsigned int st_solve_batched_rounds_max_dim(int dtype);
 
 /* ---------------------------------------------------------------------- */
 /* 3b. native multi-GPU solve (one process, ngpus devices, RCCL)           */
