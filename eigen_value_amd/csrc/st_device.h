@@ -440,6 +440,8 @@ constexpr int kNtBoth = 3;
 // m / stop contribution of vector index q of s (columns q*W .. q*W+W-1):
 // the running max, and |s_i - s_{i+1}| < eps for the W pairs that start in
 // this vector (the last pair wraps to s[0] in the cyclic semantics)
+// (tests/test_gpu_stats_positions.py pins its boundaries: the deciding pair
+// and the maximum at each vector, lane, wave, unroll, tail and wrap position)
 template <typename T, int W>
 __device__ __forceinline__ void
 stats_at(const T* __restrict__ s, const typename vec<T, W>::type& sc,
@@ -1197,6 +1199,9 @@ k_flat(T* a, const T* __restrict__ s_cur, T* __restrict__ part,
       }
     }
   }
+  // m_k / stop_k, one piece per workgroup (tests/test_gpu_stats_positions.py
+  // pins the boundaries: pairs across chunks, pieces and the ragged last
+  // piece, the split range, the wrap; test_gpu_deferred_step.py the NP forms)
   if constexpr (FS) {
     if (rg == 0) { // uniform per workgroup
       __shared__ T mx_sh[NW];
