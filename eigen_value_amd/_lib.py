@@ -201,6 +201,10 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_solve_batched_max_dim.restype = u32
     L.st_solve_batched_rounds_max_dim.argtypes = [i32]
     L.st_solve_batched_rounds_max_dim.restype = u32
+    L.max_eigen_value_vbatched_ex.argtypes = [P, i32, P, P, u32, P, P, P, P, P]
+    L.max_eigen_value_vbatched_ex.restype = i64
+    L.st_vbatched_plan.argtypes = [i32, P, u32, P, P]
+    L.st_vbatched_plan.restype = i32
     L.st_last_round_times.argtypes = [P, P, u32]
     L.st_last_round_times.restype = i32
     L.st_last_round_sums.argtypes = [P, P, u32]
@@ -219,6 +223,9 @@ def _declare(L: ctypes.CDLL) -> None:
         fb = getattr(L, f"st_solve_batched_{sfx}")
         fb.argtypes = [P, P, u32, u32, P, P, P, P, P, P, P]
         fb.restype = i64
+        fv = getattr(L, f"st_solve_vbatched_{sfx}")
+        fv.argtypes = [P, P, P, u32, P, P, P, P, P, P, P]
+        fv.restype = i64
         getattr(L, f"st_generate_hilbert_{sfx}").argtypes = [P, u32, u32, u32, P]
         getattr(L, f"st_generate_random_{sfx}").argtypes = [P, u32, u32, u32, u64, P]
         getattr(L, f"st_generate_identity_{sfx}").argtypes = [P, u32, u32, u32, P]
@@ -297,6 +304,26 @@ def batch_rounds_flag(round_loop, n: int, dtype_code: int) -> int:
     if isinstance(round_loop, str) and round_loop == "auto":
         return ST_FLAG_BATCH_ROUNDS if n > load().st_solve_batched_max_dim(dtype_code) else 0
     raise ValueError(f'round_loop must be None, True or "auto", got {round_loop!r}')
+
+
+ST_VBATCH_CLASSES = 7
+
+
+def vbatched_plan(dims, dtype_code: int, L: Optional[ctypes.CDLL] = None):
+    """The size-class plan of a variable-size batch (st_vbatched_plan; no GPU):
+    ``(order, class_first, used)`` - the matrix indices sorted by class (input
+    order kept within a class) as a uint32 array[B], where each of the
+    ST_VBATCH_CLASSES classes starts in it (uint32 array[8]) and the number
+    of non-empty classes.  Raises EigenValueError for a dim of 0 or above
+    st_solve_batched_max_dim (the message names index and dim)."""
+    import numpy as np
+    L = L or load()
+    dims = np.ascontiguousarray(dims, dtype=np.uint32)
+    order = np.zeros(len(dims), dtype=np.uint32)
+    first = np.zeros(ST_VBATCH_CLASSES + 1, dtype=np.uint32)
+    used = check(L.st_vbatched_plan(dtype_code, dims.ctypes.data, len(dims), order.ctypes.data,
+                                    first.ctypes.data), "st_vbatched_plan", L)
+    return order, first, used
 
 
 def round_sums(L: ctypes.CDLL, q, n: int, dtype):

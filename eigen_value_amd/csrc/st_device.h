@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "similarity_transform.h"
+#include "st_internal.h" // VBatchDesc
 
 #pragma clang fp contract(off)
 
@@ -2209,6 +2210,183 @@ k_solve_batched(T* a_all, T* __restrict__ v_all, uint32_t n, T eps,
         for (int j = 0; j < W; j++)
           if (lane * W + j < n)
             a[(size_t)r * n + lane * W + j] = x[i][j];
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < n)
+    v_out[threadIdx.x] = v_sh[threadIdx.x];
+}
+
+// ---------------------------------------------------------------------------
+// many small solves of DIFFERENT sizes: one launch per shape class (the
+// launcher's (WAVES, RPW) for a range of n), a workgroup per matrix of that
+// class.  The descriptor table is in plan order (sorted by class, input
+// order within a class), so workgroup blockIdx.x reads descs[first +
+// blockIdx.x]: matrix pointer, offset of its eigenvector in the packed v
+// buffer, n, and the matrix's index id = order[first + blockIdx.x] (its
+// state is states + id).  One load, indexed by blockIdx.x alone, so it and
+// everything derived from it stays in scalar registers.  The arithmetic is
+// k_solve_batched's, statement for statement, on the shape that n runs there
+// (a fork, as k_solve_batched forked k_solve_small: a shared body moved the
+// code size of two of k_solve_batched's instantiations; only the
+// addressing differs, 32-bit offsets from a global base); vec16 is
+// decided here per matrix (n % W == 0 and a 16-byte aligned base).  Both load
+// paths fill the same lanes with the same values, so an entry's bits do not
+// depend on its alignment.  The workgroups share nothing.
+// ---------------------------------------------------------------------------
+template <typename T, int ORDER, int WAVES, int RPW>
+__global__ __launch_bounds__(64 * WAVES) void
+k_solve_vbatched(const VBatchDesc* __restrict__ descs, uint32_t first,
+                 T* __restrict__ v_all, T eps, uint32_t max_itr,
+                 uint32_t semantics, st_state* states)
+{
+  constexpr int W = 16 / sizeof(T);
+  constexpr uint32_t NS = WAVES * RPW; // rows this shape holds (a multiple of W)
+  static_assert(RPW <= 64 && NS % W == 0 && NS <= small_solve_max_n<T>(),
+                "rows per wave");
+  using V = typename vec<T, W>::type;
+  __shared__ V s_sh[2][NS / W];
+  __shared__ T v_sh[NS];
+  __shared__ T inv_sh[NS]; // 1 / s_k[r], once per row instead of per lane
+  __shared__ T mx_sh[WAVES];
+  // workgroup-uniform, from blockIdx.x alone: scalar loads
+  const VBatchDesc d = descs[first + blockIdx.x];
+  const uint32_t id = d.id;
+  const uint32_t n = d.n;
+  if (n == 0 || n > NS)
+    return; // not this class's (the plan never sends one): state stays not done
+  // a pointer read from memory is a generic address to the compiler, and
+  // generic (flat) loads and stores are slower than global ones: say that it
+  // is global
+  using GT = __attribute__((address_space(1))) T;
+  using GV = __attribute__((address_space(1))) V;
+  GT* a = reinterpret_cast<GT*>(d.mat);
+  T* v_out = v_all + d.v_off;
+  st_state* state = states + id;
+  const bool vec16 = n % W == 0 && (d.mat & 15u) == 0;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t nv = (n + W - 1) / W; // chunks per row (the last one ragged)
+  const bool has = lane < nv;
+  const bool cyclic = semantics == ST_SEM_SYCL;
+  T* s0 = reinterpret_cast<T*>(s_sh[0]);
+  T* s1 = reinterpret_cast<T*>(s_sh[1]);
+  // element offset of the lane's chunk of row wave + WAVES i: off0 + i step
+  // (< 2^16, so 32 bits; step is uniform, and one register holds off0 over
+  // the whole loop where 64-bit row addresses would not fit at RPW = 16)
+  const uint32_t off0 = wave * n + lane * W;
+  const uint32_t step = WAVES * n;
+
+  V x[RPW];
+  T t[RPW];
+#pragma unroll
+  for (int i = 0; i < RPW; i++) {
+    const uint32_t r = wave + WAVES * i;
+    x[i] = (V)(T)0;
+    if (has && r < n) {
+      const uint32_t off = off0 + i * step;
+      if (vec16) {
+        x[i] = *reinterpret_cast<const GV*>(a + off);
+      } else {
+#pragma unroll
+        for (int j = 0; j < W; j++)
+          if (lane * W + j < n)
+            x[i][j] = a[off + j];
+      }
+    }
+  }
+  // K0: s_0 = rowsum(A_0)
+#pragma unroll
+  for (int i = 0; i < RPW; i++)
+    t[i] = has ? hsum<T, W>(x[i]) : (T)0;
+  wave_sum_rows<T, RPW>(t);
+  if (lane == 63) {
+#pragma unroll
+    for (int i = 0; i < RPW; i++)
+      if (wave + WAVES * i < n)
+        s0[wave + WAVES * i] = t[i];
+  }
+  if (threadIdx.x < n)
+    v_sh[threadIdx.x] = (T)1; // initialise_eigen_vector (cpp:34)
+  else if (threadIdx.x < NS)
+    s0[threadIdx.x] = s1[threadIdx.x] = (T)1; // column scale past n (never rewritten)
+
+  T* sc_ = s0;
+  T* sn_ = s1;
+  uint32_t k = 0;
+  for (;; k++) {
+    __syncthreads(); // s_k complete
+    // m_k and stop_k (find_max starts from 0, cpp:185; cpp:413-421)
+    T mx = (T)0;
+    int ok = 1;
+    if (threadIdx.x < n) {
+      const T e0 = sc_[threadIdx.x];
+      inv_sh[threadIdx.x] = (T)1 / e0;
+      mx = e0 > mx ? e0 : mx;
+      const uint32_t nx = threadIdx.x + 1;
+      if (nx < n || cyclic) {
+        const T d = e0 - sc_[nx < n ? nx : 0];
+        ok = (d < (T)0 ? -d : d) < eps ? 1 : 0;
+      }
+    }
+    mx = wave_max(mx);
+    if (lane == 0)
+      mx_sh[wave] = mx;
+    const int stop = __syncthreads_and(ok);
+    T m = mx_sh[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; w++)
+      m = mx_sh[w] > m ? mx_sh[w] : m;
+    if (threadIdx.x < n) // cpp:260
+      v_sh[threadIdx.x] = v_sh[threadIdx.x] * (sc_[threadIdx.x] / m);
+    const bool last = stop || k + 1 >= max_itr;
+    if (last && threadIdx.x == 0) {
+      state->lambda = (double)sc_[0]; // cpp:60-65
+      state->max = (double)m;
+      state->stop = stop ? 1u : 0u;
+      state->round = k;
+      state->iters = stop ? (semantics == ST_SEM_SYCL ? k : k + 1) : max_itr;
+      state->end = k + 1;
+      state->done = 1u;
+    }
+    // A_{k+1} = D_k^-1 A_k D_k and s_{k+1} (as k_round, also in the last round)
+    const V sc = has ? reinterpret_cast<const V*>(sc_)[lane] : (V)(T)1;
+#pragma unroll
+    for (int i = 0; i < RPW; i++) {
+      const uint32_t r = wave + WAVES * i;
+      const T inv = r < n ? inv_sh[r] : (T)1;
+      if constexpr (ORDER == 0)
+        x[i] = x[i] * (inv * sc); // cpp:324-325
+      else
+        x[i] = (inv * x[i]) * sc; // main.py:13-16
+      t[i] = has ? hsum<T, W>(x[i]) : (T)0;
+    }
+    wave_sum_rows<T, RPW>(t);
+    if (lane == 63) {
+#pragma unroll
+      for (int i = 0; i < RPW; i++)
+        if (wave + WAVES * i < n)
+          sn_[wave + WAVES * i] = t[i];
+    }
+    T* tmp = sc_;
+    sc_ = sn_;
+    sn_ = tmp;
+    if (last)
+      break;
+  }
+  // write back: the transformed matrix and v
+#pragma unroll
+  for (int i = 0; i < RPW; i++) {
+    const uint32_t r = wave + WAVES * i;
+    if (has && r < n) {
+      const uint32_t off = off0 + i * step;
+      if (vec16) {
+        *reinterpret_cast<GV*>(a + off) = x[i];
+      } else {
+#pragma unroll
+        for (int j = 0; j < W; j++)
+          if (lane * W + j < n)
+            a[off + j] = x[i][j];
       }
     }
   }

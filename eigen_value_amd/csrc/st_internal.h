@@ -153,5 +153,30 @@ template <typename T>
 int launch_solve_batched(T* a, T* v, uint32_t batch, uint32_t n, T eps,
                          uint32_t max_itr, uint32_t semantics, st_state* st,
                          hipStream_t stream);
+// The workgroup shape classes of the two launchers above and below:
+// class c holds n <= 4 << c (4, 8, 16, 32, 64, 128, 256; the last fp32
+// only).  solve_shape_class(n) is the one place that maps n to its class;
+// kSolveShapeClasses is returned for an n beyond all of them.
+constexpr uint32_t kSolveShapeClasses = 7;
+uint32_t solve_shape_class(uint32_t n);
+// one matrix of a variable-size batch, as k_solve_vbatched reads it
+struct VBatchDesc
+{
+  uint64_t mat;   // device address of the n x n row-major matrix
+  uint64_t v_off; // element offset of its eigenvector in the packed v buffer
+  uint32_t n;
+  uint32_t id;    // its index in the caller's arrays (and in the state array)
+};
+static_assert(sizeof(VBatchDesc) == 24, "descriptor layout");
+// one shape class of a variable-size batch in one launch (k_solve_vbatched):
+// descs is the device table in plan order (descs[j] describes matrix
+// order[j]); workgroup i solves the matrix of descs[first + i] (i < count,
+// every one of class cls) as launch_solve_batched's workgroup would, v to
+// v + v_off, the result to st[id]
+template <typename T>
+int launch_solve_vbatched(const VBatchDesc* descs, uint32_t first,
+                          uint32_t count, uint32_t cls, T* v, T eps,
+                          uint32_t max_itr, uint32_t semantics, st_state* st,
+                          hipStream_t stream);
 
 } // namespace st

@@ -1714,7 +1714,58 @@ solve_batched_max_n()
 }
 
 // workgroup shape per n: the fewest waves (4 / 8 / 16) that hold the matrix
-// at <= 16 rows each, rows per wave the power of two >= ceil(n / waves)
+// at <= 16 rows each, rows per wave the power of two >= ceil(n / waves).
+// Seven classes (n <= 4, 8, 16, 32, 64, 128, 256); launch_solve_batched and
+// launch_solve_vbatched both choose through solve_shape_class /
+// solve_shape_dispatch, so a matrix of a mixed batch runs the shape it runs
+// in a uniform one.
+static_assert(kSolveShapeClasses == ST_VBATCH_CLASSES, "class count");
+
+uint32_t
+solve_shape_class(uint32_t n)
+{
+  uint32_t cls = 0;
+  while (cls < kSolveShapeClasses && n > (4u << cls))
+    cls++;
+  return cls; // kSolveShapeClasses: beyond every class
+}
+
+// go(waves, rows per wave) for class `cls`; false where T has no such class
+template <typename T, typename F>
+static bool
+solve_shape_dispatch(uint32_t cls, F&& go)
+{
+  using std::integral_constant;
+  switch (cls) {
+    case 0:
+      go(integral_constant<int, 4>{}, integral_constant<int, 1>{});
+      return true;
+    case 1:
+      go(integral_constant<int, 4>{}, integral_constant<int, 2>{});
+      return true;
+    case 2:
+      go(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+      return true;
+    case 3:
+      go(integral_constant<int, 4>{}, integral_constant<int, 8>{});
+      return true;
+    case 4:
+      go(integral_constant<int, 4>{}, integral_constant<int, 16>{});
+      return true;
+    case 5:
+      go(integral_constant<int, 8>{}, integral_constant<int, 16>{});
+      return true;
+    case 6:
+      if constexpr (sizeof(T) == 4) {
+        go(integral_constant<int, 16>{}, integral_constant<int, 16>{});
+        return true;
+      }
+      return false;
+    default:
+      return false;
+  }
+}
+
 template <typename T>
 int
 launch_solve_batched(T* a, T* v, uint32_t batch, uint32_t n, T eps,
@@ -1731,35 +1782,53 @@ launch_solve_batched(T* a, T* v, uint32_t batch, uint32_t n, T eps,
              semantics);
   ST_REQUIRE(max_itr > 0, "solve_batched: max_itr must be > 0");
   const uint32_t vec = (n % W == 0 && aligned16(a)) ? 1u : 0u;
-  auto go = [&](auto order, auto waves, auto rpw) {
-    constexpr int WV = decltype(waves)::value;
-    hipLaunchKernelGGL(
-      (dev::k_solve_batched<T, decltype(order)::value, WV, decltype(rpw)::value>),
-      dim3(batch), dim3(64 * WV), 0, stream, a, v, n, eps, max_itr, semantics,
-      st, vec);
-  };
   auto by_shape = [&](auto order) {
-    using std::integral_constant;
-    if (n <= 4)
-      go(order, integral_constant<int, 4>{}, integral_constant<int, 1>{});
-    else if (n <= 8)
-      go(order, integral_constant<int, 4>{}, integral_constant<int, 2>{});
-    else if (n <= 16)
-      go(order, integral_constant<int, 4>{}, integral_constant<int, 4>{});
-    else if (n <= 32)
-      go(order, integral_constant<int, 4>{}, integral_constant<int, 8>{});
-    else if (n <= 64)
-      go(order, integral_constant<int, 4>{}, integral_constant<int, 16>{});
-    else if (n <= 128)
-      go(order, integral_constant<int, 8>{}, integral_constant<int, 16>{});
-    else if constexpr (sizeof(T) == 4)
-      go(order, integral_constant<int, 16>{}, integral_constant<int, 16>{});
+    return solve_shape_dispatch<T>(solve_shape_class(n), [&](auto waves, auto rpw) {
+      constexpr int WV = decltype(waves)::value;
+      hipLaunchKernelGGL(
+        (dev::k_solve_batched<T, decltype(order)::value, WV, decltype(rpw)::value>),
+        dim3(batch), dim3(64 * WV), 0, stream, a, v, n, eps, max_itr, semantics,
+        st, vec);
+    });
   };
-  if (semantics == ST_SEM_MAINPY)
-    by_shape(std::integral_constant<int, 1>{});
-  else
-    by_shape(std::integral_constant<int, 0>{});
+  const bool ok = semantics == ST_SEM_MAINPY
+                    ? by_shape(std::integral_constant<int, 1>{})
+                    : by_shape(std::integral_constant<int, 0>{});
+  ST_REQUIRE(ok, "solve_batched: no workgroup shape for n = %u", n);
   return check_launch("solve_batched");
+}
+
+// One shape class of a variable-size batch (k_solve_vbatched): workgroup i
+// solves the matrix of descs[first + i], i < count, all of class `cls`.
+// descs: the device table in plan order; v: the packed eigenvectors;
+// st[batch], indexed by matrix.
+template <typename T>
+int
+launch_solve_vbatched(const VBatchDesc* descs, uint32_t first, uint32_t count,
+                      uint32_t cls, T* v, T eps, uint32_t max_itr,
+                      uint32_t semantics, st_state* st, hipStream_t stream)
+{
+  ST_REQUIRE(descs && v && st, "solve_vbatched: null pointer");
+  ST_REQUIRE(count > 0 && count <= 0x7fffffffu,
+             "solve_vbatched: count = %u outside 1 .. 2^31 - 1", count);
+  ST_REQUIRE(semantics <= ST_SEM_MAINPY, "solve_vbatched: bad semantics %u",
+             semantics);
+  ST_REQUIRE(max_itr > 0, "solve_vbatched: max_itr must be > 0");
+  auto by_shape = [&](auto order_c) {
+    return solve_shape_dispatch<T>(cls, [&](auto waves, auto rpw) {
+      constexpr int WV = decltype(waves)::value;
+      hipLaunchKernelGGL(
+        (dev::k_solve_vbatched<T, decltype(order_c)::value, WV,
+                               decltype(rpw)::value>),
+        dim3(count), dim3(64 * WV), 0, stream,
+        descs, first, v, eps, max_itr, semantics, st);
+    });
+  };
+  const bool ok = semantics == ST_SEM_MAINPY
+                    ? by_shape(std::integral_constant<int, 1>{})
+                    : by_shape(std::integral_constant<int, 0>{});
+  ST_REQUIRE(ok, "solve_vbatched: no workgroup shape for class %u", cls);
+  return check_launch("solve_vbatched");
 }
 
 template uint32_t solve_batched_max_n<float>();
@@ -1770,6 +1839,13 @@ template int launch_solve_batched<float>(float*, float*, uint32_t, uint32_t,
 template int launch_solve_batched<double>(double*, double*, uint32_t, uint32_t,
                                           double, uint32_t, uint32_t,
                                           st_state*, hipStream_t);
+template int launch_solve_vbatched<float>(const VBatchDesc*, uint32_t, uint32_t,
+                                          uint32_t, float*, float, uint32_t,
+                                          uint32_t, st_state*, hipStream_t);
+template int launch_solve_vbatched<double>(const VBatchDesc*, uint32_t,
+                                           uint32_t, uint32_t, double*, double,
+                                           uint32_t, uint32_t, st_state*,
+                                           hipStream_t);
 template bool solve_small_fits<float>(const float*, uint32_t);
 template bool solve_small_fits<double>(const double*, uint32_t);
 template int launch_solve_small<float>(float*, float*, uint32_t, float,

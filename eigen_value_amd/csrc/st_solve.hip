@@ -97,7 +97,21 @@ struct Context
   size_t bsum_bytes = 0;
   uint32_t* d_bcount = nullptr;
   uint32_t* h_bcount = nullptr;
+  // variable-size batch: the descriptor table (plan order) for vb_cap
+  // matrices, staged in pinned memory and copied to the device once per call
+  // (every call ends in a stream sync, so the staging is free again when the
+  // next one fills it)
+  void* h_vb = nullptr;
+  void* d_vb = nullptr;
+  size_t vb_cap = 0; // matrices
 };
+
+// bytes of the descriptor table for `count` matrices
+constexpr size_t
+vb_bytes(size_t count)
+{
+  return count * sizeof(VBatchDesc);
+}
 
 double
 ms_since(std::chrono::steady_clock::time_point t0)
@@ -195,6 +209,27 @@ ensure_bstate(Context* c, size_t count)
   }
   ST_CHECK(hipMalloc((void**)&c->d_bstate, count * sizeof(st_state)));
   c->bstate_cap = count;
+  return 0;
+}
+
+int
+ensure_vbatch(Context* c, size_t count)
+{
+  if (c->h_vb && c->d_vb && c->vb_cap >= count)
+    return 0;
+  if (c->h_vb || c->d_vb) {
+    ST_CHECK(hipStreamSynchronize(c->stream));
+    if (c->h_vb)
+      ST_CHECK(hipHostFree(c->h_vb));
+    c->h_vb = nullptr;
+    if (c->d_vb)
+      ST_CHECK(hipFree(c->d_vb));
+    c->d_vb = nullptr;
+    c->vb_cap = 0;
+  }
+  ST_CHECK(hipHostMalloc(&c->h_vb, vb_bytes(count), hipHostMallocDefault));
+  ST_CHECK(hipMalloc(&c->d_vb, vb_bytes(count)));
+  c->vb_cap = count;
   return 0;
 }
 
@@ -775,6 +810,214 @@ solve_batched_host(Context* c, const T* mats, uint32_t batch, uint32_t n,
   return (int64_t)(h2d + local.loop_ms);
 }
 
+// The size-class plan of a variable-size batch (pure host code): a stable
+// counting sort of the indices by solve_shape_class(dims[b]).  order[batch],
+// class_first[kSolveShapeClasses + 1].  Returns the number of non-empty
+// classes or -1 (a dim of 0 or above max_n, named with its index).
+int
+vbatched_plan(uint32_t max_n, const uint32_t* dims, uint32_t batch,
+              uint32_t* order, uint32_t* class_first)
+{
+  uint32_t count[kSolveShapeClasses] = {};
+  for (uint32_t b = 0; b < batch; b++) {
+    ST_REQUIRE(dims[b] > 0, "vbatched solve: dims[%u] = 0, dim must be > 0", b);
+    ST_REQUIRE(dims[b] <= max_n,
+               "vbatched solve: dims[%u] = %u exceeds the one-workgroup limit "
+               "%u (st_solve_batched_max_dim)", b, dims[b], max_n);
+    count[solve_shape_class(dims[b])]++;
+  }
+  uint32_t next[kSolveShapeClasses];
+  int used = 0;
+  class_first[0] = 0;
+  for (uint32_t k = 0; k < kSolveShapeClasses; k++) {
+    next[k] = class_first[k];
+    class_first[k + 1] = class_first[k] + count[k];
+    used += count[k] ? 1 : 0;
+  }
+  for (uint32_t b = 0; b < batch; b++)
+    order[next[solve_shape_class(dims[b])]++] = b;
+  return used;
+}
+
+// what both variable-size entry points reject before touching the device
+template <typename T>
+int
+vbatched_args(Context* c, uint32_t batch, const st_options* opt, Resolved* o)
+{
+  ST_REQUIRE(c, "null queue");
+  if (resolve<T>(opt, o))
+    return -1;
+  constexpr uint32_t kNoVBatch = ST_FLAG_MATRIX_FREE | ST_FLAG_TIME_KERNELS |
+                                 ST_FLAG_TRACE_SUMS | ST_FLAG_ROUND_LOOP |
+                                 ST_FLAG_BATCH_ROUNDS;
+  ST_REQUIRE((o->flags & kNoVBatch) == 0,
+             "vbatched solve: ST_FLAG_MATRIX_FREE, ST_FLAG_TIME_KERNELS, "
+             "ST_FLAG_TRACE_SUMS, ST_FLAG_ROUND_LOOP and ST_FLAG_BATCH_ROUNDS "
+             "are not supported (flags = %u)", o->flags);
+  ST_REQUIRE(batch <= 0x7fffffffu,
+             "vbatched solve: batch = %u exceeds the grid limit 2^31 - 1", batch);
+  return 0;
+}
+
+// Many small solves of different sizes: one k_solve_vbatched launch per
+// non-empty shape class, largest class first, back to back on the stream.
+// Per call: the plan, the descriptor table filled in plan order in pinned
+// staging, one copy of it to the device, one memset of the states, the
+// class launches, one stream sync, one state read-back.
+template <typename T>
+int64_t
+solve_vbatched(Context* c, T* const* mat_ptrs, const uint32_t* dims,
+               uint32_t batch, T* d_v_out, T* v_host, T* eigen_vals,
+               uint32_t* iter_cnts, uint32_t* converged, const st_options* opt,
+               st_stats* stats)
+{
+  Resolved o;
+  if (vbatched_args<T>(c, batch, opt, &o))
+    return -1;
+  if (stats)
+    std::memset(stats, 0, sizeof(*stats));
+  if (batch == 0) { // nothing to solve
+    if (stats)
+      stats->converged = 1;
+    return 0;
+  }
+  ST_REQUIRE(mat_ptrs && dims, "null matrix pointer array or dims");
+  ST_REQUIRE(eigen_vals && iter_cnts, "null output pointer");
+  ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
+  // everything that can be refused is refused here, before the first enqueue
+  std::vector<uint32_t> order(batch);
+  uint32_t class_first[kSolveShapeClasses + 1];
+  const int used = vbatched_plan(solve_batched_max_n<T>(), dims, batch,
+                                 order.data(), class_first);
+  if (used < 0)
+    return -1;
+  for (uint32_t b = 0; b < batch; b++)
+    ST_REQUIRE(mat_ptrs[b], "vbatched solve: d_mat_ptrs[%u] is NULL", b);
+  size_t v_elems = 0;
+  for (uint32_t b = 0; b < batch; b++)
+    v_elems += dims[b];
+  const size_t v_bytes = sizeof(T) * v_elems;
+  if (ensure_device(c) || ensure_bstate(c, batch) || ensure_vbatch(c, batch) ||
+      (!d_v_out && ensure_part(c, v_bytes))) // d_part: free outside flat rounds
+    return -1;
+  T* d_v = d_v_out ? d_v_out : reinterpret_cast<T*>(c->d_part);
+  hipStream_t s = c->stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  // the table in plan order: entry j describes matrix order[j] (the
+  // eigenvector offsets follow the input order)
+  VBatchDesc* h_desc = reinterpret_cast<VBatchDesc*>(c->h_vb);
+  std::vector<uint64_t> v_off(batch);
+  size_t off = 0;
+  for (uint32_t b = 0; b < batch; b++) {
+    v_off[b] = off;
+    off += dims[b];
+  }
+  for (uint32_t j = 0; j < batch; j++) {
+    const uint32_t b = order[j];
+    h_desc[j] = VBatchDesc{ (uint64_t) reinterpret_cast<uintptr_t>(mat_ptrs[b]),
+                            v_off[b], dims[b], b };
+  }
+  ST_CHECK(hipMemcpyAsync(c->d_vb, c->h_vb, vb_bytes(batch),
+                          hipMemcpyHostToDevice, s));
+  const VBatchDesc* d_desc = reinterpret_cast<const VBatchDesc*>(c->d_vb);
+  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)batch, s));
+  uint32_t launches = 0;
+  for (uint32_t k = kSolveShapeClasses; k-- > 0;) {
+    const uint32_t count = class_first[k + 1] - class_first[k];
+    if (!count)
+      continue;
+    if (launch_solve_vbatched<T>(d_desc, class_first[k], count, k, d_v,
+                                 (T)o.eps, o.max_itr, o.semantics, c->d_bstate,
+                                 s))
+      return -1;
+    launches++;
+  }
+  ST_CHECK(hipStreamSynchronize(s));
+  c->h_bstate.resize(batch);
+  ST_CHECK(hipMemcpy(c->h_bstate.data(), c->d_bstate,
+                     sizeof(st_state) * (size_t)batch, hipMemcpyDeviceToHost));
+  const double loop_ms = ms_since(t0);
+
+  const auto t1 = std::chrono::steady_clock::now();
+  uint32_t rounds = 0, all = 1;
+  for (uint32_t b = 0; b < batch; b++) {
+    const st_state& fin = c->h_bstate[b];
+    ST_REQUIRE(fin.done, "internal: matrix %u ended without done flag", b);
+    eigen_vals[b] = (T)fin.lambda;
+    iter_cnts[b] = fin.iters;
+    if (converged)
+      converged[b] = fin.stop;
+    rounds = fin.end > rounds ? fin.end : rounds;
+    all &= fin.stop;
+  }
+  if (v_host)
+    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
+  const double d2h_ms = ms_since(t1);
+  if (stats) {
+    stats->loop_ms = loop_ms;
+    stats->d2h_ms = d2h_ms;
+    stats->rounds = rounds;
+    stats->converged = all;
+    stats->fused_launches = launches;
+  }
+  return (int64_t)loop_ms;
+}
+
+// host-pointer twin: [tightly packed mats | v] staged in the context's matrix
+// buffer, matrix b at element offset sum_{j<b} dims[j]^2
+template <typename T>
+int64_t
+solve_vbatched_host(Context* c, const T* mats, const uint32_t* dims,
+                    uint32_t batch, T* eigen_vals, T* eigen_vecs,
+                    uint32_t* iter_cnts, const st_options* opt, st_stats* stats)
+{
+  Resolved o;
+  if (vbatched_args<T>(c, batch, opt, &o))
+    return -1;
+  if (batch == 0) // the no-op, with its stats
+    return solve_vbatched<T>(c, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                             nullptr, nullptr, opt, stats);
+  ST_REQUIRE(mats && dims && eigen_vals && eigen_vecs && iter_cnts,
+             "null pointer");
+  // the dims, before they size anything (the solve checks them again)
+  {
+    std::vector<uint32_t> order(batch);
+    uint32_t class_first[kSolveShapeClasses + 1];
+    if (vbatched_plan(solve_batched_max_n<T>(), dims, batch, order.data(),
+                      class_first) < 0)
+      return -1;
+  }
+  size_t m_elems = 0, v_elems = 0;
+  for (uint32_t b = 0; b < batch; b++) {
+    m_elems += (size_t)dims[b] * dims[b];
+    v_elems += dims[b];
+  }
+  const size_t bytes = (sizeof(T) * m_elems + 255) & ~(size_t)255; // v stays aligned
+  if (ensure_device(c) || ensure_matrix(c, bytes + sizeof(T) * v_elems))
+    return -1;
+  T* d_mats = reinterpret_cast<T*>(c->d_mat);
+  T* d_v = reinterpret_cast<T*>((char*)c->d_mat + bytes);
+  std::vector<T*> ptrs(batch);
+  size_t off = 0;
+  for (uint32_t b = 0; b < batch; b++) {
+    ptrs[b] = d_mats + off;
+    off += (size_t)dims[b] * dims[b];
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(c->d_mat, mats, sizeof(T) * m_elems,
+                          hipMemcpyHostToDevice, c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  if (solve_vbatched<T>(c, ptrs.data(), dims, batch, d_v, eigen_vecs,
+                        eigen_vals, iter_cnts, nullptr, opt, &local) < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
+}
+
 Context*
 as_ctx(void* wq)
 {
@@ -883,6 +1126,10 @@ destroy_queue(void* wq)
     (void)hipFree(c->d_bcount);
   if (c->h_bcount)
     (void)hipHostFree(c->h_bcount);
+  if (c->d_vb)
+    (void)hipFree(c->d_vb);
+  if (c->h_vb)
+    (void)hipHostFree(c->h_vb);
   if (c->h_state)
     (void)hipHostFree(c->h_state);
   for (hipEvent_t e : c->ev_flag)
@@ -1056,6 +1303,68 @@ max_eigen_value_batched_ex(void* wq, int dtype, const void* mats,
       (double*)eigen_vecs, iter_cnts, opt, stats);
   st::set_error("max_eigen_value_batched_ex: dtype must be 0 (f32) or 1 (f64)");
   return -1;
+}
+
+int64_t
+st_solve_vbatched_f32(void* wq, float* const* d_mat_ptrs, const uint32_t* dims,
+                      unsigned int batch, float* d_eigen_vecs,
+                      float* eigen_vecs_host, float* eigen_vals,
+                      unsigned int* iter_cnts, unsigned int* converged,
+                      const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_vbatched<float>(st::as_ctx(wq), d_mat_ptrs, dims, batch,
+                                   d_eigen_vecs, eigen_vecs_host, eigen_vals,
+                                   iter_cnts, converged, opt, stats);
+}
+
+int64_t
+st_solve_vbatched_f64(void* wq, double* const* d_mat_ptrs, const uint32_t* dims,
+                      unsigned int batch, double* d_eigen_vecs,
+                      double* eigen_vecs_host, double* eigen_vals,
+                      unsigned int* iter_cnts, unsigned int* converged,
+                      const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_vbatched<double>(st::as_ctx(wq), d_mat_ptrs, dims, batch,
+                                    d_eigen_vecs, eigen_vecs_host, eigen_vals,
+                                    iter_cnts, converged, opt, stats);
+}
+
+int64_t
+max_eigen_value_vbatched_ex(void* wq, int dtype, const void* mats,
+                            const uint32_t* dims, unsigned int batch,
+                            void* eigen_vals, void* eigen_vecs,
+                            unsigned int* iter_cnts, const st_options* opt,
+                            st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (dtype == 0)
+    return st::solve_vbatched_host<float>(
+      st::as_ctx(wq), (const float*)mats, dims, batch, (float*)eigen_vals,
+      (float*)eigen_vecs, iter_cnts, opt, stats);
+  if (dtype == 1)
+    return st::solve_vbatched_host<double>(
+      st::as_ctx(wq), (const double*)mats, dims, batch, (double*)eigen_vals,
+      (double*)eigen_vecs, iter_cnts, opt, stats);
+  st::set_error("max_eigen_value_vbatched_ex: dtype must be 0 (f32) or 1 (f64)");
+  return -1;
+}
+
+int
+st_vbatched_plan(int dtype, const uint32_t* dims, unsigned int batch,
+                 uint32_t* order_out, uint32_t* class_first)
+{
+  st::clear_error();
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "st_vbatched_plan: dtype must be 0 (f32) or 1 (f64)");
+  ST_REQUIRE(class_first && ((dims && order_out) || batch == 0),
+             "st_vbatched_plan: null pointer");
+  return st::vbatched_plan(st_solve_batched_max_dim(dtype), dims, batch,
+                           order_out, class_first);
 }
 
 unsigned int

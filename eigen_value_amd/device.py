@@ -494,6 +494,81 @@ class DeviceSolver:
         out["converged_each"] = conv
         return (torch.from_numpy(lam), v, torch.from_numpy(it.astype(np.int64)), out)
 
+    def solve_vbatched(self, mats, *, inplace: bool = False, eps: Optional[float] = None,
+                       max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL):
+        """Many small matrices of DIFFERENT sizes in one call
+        (``st_solve_vbatched_*``): one launch per workgroup-shape class
+        (n <= 4, 8, 16, 32, 64, 128, 256), a workgroup per matrix.  ``mats``:
+        a sequence of square 2-D torch tensors (or DLPack producers) of one
+        dtype on this solver's device, each n <= ``batched_max_dim``; an empty
+        sequence is allowed.
+
+        With ``inplace`` every matrix must be contiguous and is transformed
+        where it lies (its own storage pointer is passed, nothing is
+        concatenated; the matrices must not overlap).  Otherwise they are
+        copied into one workspace, each at a 16-byte aligned offset, and the
+        inputs stay untouched.
+
+        Returns (λ: host tensor[B], vs: list of B device views into one
+        packed v tensor, iterations: host tensor[B] (int64), stats: dict).
+        ``stats["converged_each"]`` is a uint32 array[B], ``stats["rounds"]``
+        the largest round count, ``stats["fused_launches"]`` the number of
+        class launches.  Every entry equals ``solve_batched`` on that matrix
+        alone as a (1, n, n) batch bit for bit, whatever its alignment."""
+        import numpy as np
+        torch = _torch()
+        mats = [torch.from_dlpack(m) if not isinstance(m, torch.Tensor) and hasattr(m, "__dlpack__")
+                else m for m in mats]
+        _check_cuda(*mats)
+        here = (self.device.index if self.device.index is not None
+                else torch.cuda.current_device())
+        dtype = mats[0].dtype if mats else torch.float32
+        for m in mats:
+            if m.device.index != here:
+                raise ValueError(f"matrix on {m.device}, solver context on {self.device}")
+            assert m.dim() == 2 and m.shape[0] == m.shape[1], "must be square"
+            if m.dtype != dtype:
+                raise TypeError(f"one dtype required, got {dtype} and {m.dtype}")
+            if inplace and not m.is_contiguous():
+                raise ValueError("inplace needs contiguous (row-major) matrices")
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"float32/float64 tensor required, got {dtype}")
+        sfx = "f64" if dtype == torch.float64 else "f32"
+        b = len(mats)
+        dims = np.array([m.shape[0] for m in mats], dtype=np.uint32)
+        dev_ = torch.device("cuda", here)
+        if inplace:
+            work = mats
+        else:
+            # one workspace, each matrix at a 16-byte aligned offset
+            per16 = 16 // (8 if sfx == "f64" else 4)
+            offs, total = [], 0
+            for n in dims.tolist():
+                offs.append(total)
+                total += -(-n * n // per16) * per16
+            space = torch.empty(total, dtype=dtype, device=dev_)
+            work = [space[o:o + n * n].view(n, n) for o, n in zip(offs, dims.tolist())]
+            for w, m in zip(work, mats):
+                w.copy_(m)
+        ptrs = (ctypes.c_void_p * max(1, b))(*[_ptr(w) for w in work])
+        voff = np.concatenate([[0], np.cumsum(dims, dtype=np.int64)])
+        v = torch.empty(int(voff[-1]), dtype=dtype, device=dev_)
+        npdt = np.float64 if sfx == "f64" else np.float32
+        lam = np.zeros(b, dtype=npdt)
+        it = np.zeros(b, dtype=np.uint32)
+        conv = np.zeros(b, dtype=np.uint32)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics, 0, 0)
+        stats = _lib.st_stats()
+        _lib.check(self.L.st_set_stream(self.q, _stream(dev_)), "st_set_stream")
+        rc = getattr(self.L, f"st_solve_vbatched_{sfx}")(
+            self.q, ptrs, dims.ctypes.data, b, _ptr(v) if b else None, None, lam.ctypes.data,
+            it.ctypes.data, conv.ctypes.data, ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(rc, "st_solve_vbatched")
+        out = stats.as_dict()
+        out["converged_each"] = conv
+        vs = [v[int(voff[i]):int(voff[i + 1])] for i in range(b)]
+        return (torch.from_numpy(lam), vs, torch.from_numpy(it.astype(np.int64)), out)
+
     def last_round_sums(self):
         """Row sums s_0 .. s_{rounds-1} of the last ``solve(trace_sums=True)``
         as a (rounds, n) numpy array (empty if that solve was not traced)."""

@@ -148,6 +148,44 @@ class EigenValue:
         _lib.check(ts, "max_eigen_value_batched_ex", self.so_lib)
         return eigen_vals, eigen_vecs, int(ts), iter_cnts
 
+    def similarity_transform_vbatched(self, mats, *, eps: Optional[float] = None,
+                                      max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL):
+        """Many small matrices of DIFFERENT sizes in one call
+        (``max_eigen_value_vbatched_ex``): ``mats`` is a sequence of square
+        float32 or float64 arrays of one dtype, each n up to
+        ``st_solve_batched_max_dim`` (256 / 128); an empty sequence is allowed.
+        They are packed into one buffer, copied once, and solved with one
+        launch per workgroup-shape class.  Every matrix is solved exactly as
+        ``similarity_transform_batched`` would solve it as a batch of one.
+
+        Returns ``(λ[B], [v_0 .. v_{B-1}], ts_ms, iterations[B])``: λ of the
+        input dtype (float32 for an empty sequence), a list of B eigenvector
+        arrays, ``uint32`` counts."""
+        mats = list(mats)
+        for m in mats:
+            assert isinstance(m, np.ndarray) and m.ndim == 2 and m.shape[0] == m.shape[1], \
+                "must be square matrices of floating points !"
+        dt = mats[0].dtype if mats else np.dtype(np.float32)
+        for m in mats:
+            assert m.dtype == dt, "all matrices must have one dtype !"
+        assert dt.num in (11, 12), "dtype of input matrices must be float32 or float64 !"
+        b = len(mats)
+        dims = np.array([m.shape[0] for m in mats], dtype=np.uint32)
+        packed = (np.concatenate([np.ravel(m) for m in mats]) if b else np.zeros(0, dt))
+        packed = np.ascontiguousarray(packed, dtype=dt)
+        offs = np.concatenate([[0], np.cumsum(dims, dtype=np.int64)])
+        eigen_vals = np.empty(b, dtype=dt)
+        eigen_vecs = np.empty(int(offs[-1]), dtype=dt)
+        iter_cnts = np.zeros(b, dtype=np.uint32)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics, 0, 0)
+        dtype = _lib.DTYPE_F32 if dt == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_vbatched_ex(
+            self.sycl_q, dtype, packed.ctypes.data, dims.ctypes.data, b, eigen_vals.ctypes.data,
+            eigen_vecs.ctypes.data, iter_cnts.ctypes.data, ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_vbatched_ex", self.so_lib)
+        vs = [eigen_vecs[int(offs[i]):int(offs[i + 1])] for i in range(b)]
+        return eigen_vals, vs, int(ts), iter_cnts
+
     def last_round_times(self) -> np.ndarray:
         """Per-round kernel times (ms) of the last ``similarity_transform_ex``
         call made with ``time_kernels=True`` (empty otherwise)."""

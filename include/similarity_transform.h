@@ -249,6 +249,64 @@ unsigned int st_solve_batched_max_dim(int dtype);
  * 4344; anything else: 0), derived from st_round_flat_pays.  No GPU needed. */
 unsigned int st_solve_batched_rounds_max_dim(int dtype);
 
+/* Variable-size batch ("vbatched"): `batch` independent solves of matrices of
+ * DIFFERENT dims in one call.  The batch is split into at most
+ * ST_VBATCH_CLASSES workgroup-shape classes (dim <= 4, 8, 16, 32, 64, 128,
+ * 256; the last fp32 only), the classes st_solve_batched_* chooses from, and
+ * each non-empty class is one launch (k_solve_vbatched), a workgroup per
+ * matrix, largest class first.
+ * d_mat_ptrs: HOST array [batch] of device pointers, matrix b is dims[b] x
+ * dims[b], row-major, contiguous, TRANSFORMED IN PLACE to its own A_end; the
+ * matrices must not overlap.  dims: HOST array [batch], each 1 ..
+ * st_solve_batched_max_dim.  Eigenvectors are packed: matrix b's at element
+ * offset sum_{j<b} dims[j] of d_eigen_vecs (device) and/or eigen_vecs_host.
+ * eigen_vals / iter_cnts / converged (may be NULL): host [batch], input
+ * order.  Every entry's eigen_val, eigenvector, iter_cnt, converged flag and
+ * final matrix are bit-identical to st_solve_batched_* on that matrix alone
+ * (batch = 1), whatever its alignment: a matrix whose dim is a multiple of
+ * 16 / sizeof(element) and whose pointer is 16-byte aligned is loaded and
+ * stored 16 bytes at a time, any other element-wide, into the same lanes.
+ * opt as for st_solve_batched_*; ST_FLAG_BATCH_ROUNDS is an error here as are
+ * the four flags that are errors there; a dim of 0 or above the limit and a
+ * NULL matrix pointer are errors naming the index, never a fallback and never
+ * a partial solve (checked before anything is enqueued).  batch == 0: no-op
+ * returning 0.  stats->fused_launches = the number of class launches.
+ * Returns loop ms or negative. */
+int64_t st_solve_vbatched_f32(void* wq, float* const* d_mat_ptrs,
+                              const uint32_t* dims, unsigned int batch,
+                              float* d_eigen_vecs, float* eigen_vecs_host,
+                              float* eigen_vals, unsigned int* iter_cnts,
+                              unsigned int* converged, const st_options* opt,
+                              st_stats* stats);
+int64_t st_solve_vbatched_f64(void* wq, double* const* d_mat_ptrs,
+                              const uint32_t* dims, unsigned int batch,
+                              double* d_eigen_vecs, double* eigen_vecs_host,
+                              double* eigen_vals, unsigned int* iter_cnts,
+                              unsigned int* converged, const st_options* opt,
+                              st_stats* stats);
+/* Host twin: mats = ONE host buffer holding the matrices tightly packed in
+ * input order (matrix b at element offset sum_{j<b} dims[j]^2), read only;
+ * one H2D copy.  dtype: 0 = float32, 1 = float64.  eigen_vals [batch],
+ * eigen_vecs (packed as above), iter_cnts [batch]: host pointers.  The tight
+ * packing leaves some matrices off 16-byte alignment on the device; those
+ * take the element-wide path (same bits, see above).  Returns h2d + loop ms
+ * or negative. */
+int64_t max_eigen_value_vbatched_ex(void* wq, int dtype, const void* mats,
+                                    const uint32_t* dims, unsigned int batch,
+                                    void* eigen_vals, void* eigen_vecs,
+                                    unsigned int* iter_cnts,
+                                    const st_options* opt, st_stats* stats);
+#define ST_VBATCH_CLASSES 7
+/* Size-class plan of a variable-size batch for dtype (0 f32, 1 f64):
+ * order_out[batch] = the matrix indices sorted by class, input order kept
+ * within a class; class_first[ST_VBATCH_CLASSES + 1] = where each class
+ * starts in order_out (empty classes have equal neighbours).  Returns the
+ * number of non-empty classes, or negative (dim 0 or above
+ * st_solve_batched_max_dim: the message names the index and the dim; bad
+ * dtype; null pointer).  No GPU needed. */
+int st_vbatched_plan(int dtype, const uint32_t* dims, unsigned int batch,
+                     uint32_t* order_out, uint32_t* class_first);
+
 /* ---------------------------------------------------------------------- */
 /* 3b. native multi-GPU solve (one process, ngpus devices, RCCL)           */
 /* ---------------------------------------------------------------------- */
