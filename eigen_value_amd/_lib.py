@@ -31,6 +31,9 @@ ST_MAX_ITR = 1000
 
 DTYPE_F32 = 0
 DTYPE_F64 = 1
+# storage codes of the half-precision entry points (*_half, st_narrow_f32)
+ST_STORE_F16 = 2
+ST_STORE_BF16 = 3
 
 
 class EigenValueError(RuntimeError):
@@ -289,6 +292,20 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_launch_policy_query.restype = i32
     L.st_state_reset.argtypes = [P, P]
     L.st_state_reset.restype = i32
+    # half-precision storage (fp16 / bf16 matrix, fp32 vectors)
+    L.st_rowsum_half.argtypes = [i32, P, P, u32, u32, P]
+    L.st_rowsum_half.restype = i32
+    L.st_mfree_round_half.argtypes = [i32, P, P, P, P, P, u32, u32, u32, f32, u32, u32, u32,
+                                      P, P]
+    L.st_mfree_round_half.restype = i32
+    L.st_narrow_f32.argtypes = [i32, P, P, u64, P]
+    L.st_narrow_f32.restype = i32
+    L.st_solve_device_half.argtypes = [P, i32, P, u32, P, P, P, P, P, P]
+    L.st_solve_device_half.restype = i64
+    L.max_eigen_value_half_ex.argtypes = [P, i32, P, P, P, u32, P, P, P]
+    L.max_eigen_value_half_ex.restype = i64
+    L.st_half_shape_desc.argtypes = []
+    L.st_half_shape_desc.restype = ctypes.c_char_p
 
 
 def batch_rounds_flag(round_loop, n: int, dtype_code: int) -> int:

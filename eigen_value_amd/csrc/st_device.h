@@ -757,13 +757,16 @@ k_round_batched(T* a, const T* s_cur, T* s_next, T* v, uint32_t ng_main,
 // The batched round loop's per-batch look at the finished counter: one lane
 // copies it to the caller's pinned, host-coherent word with a system-scope
 // vector store, in stream order behind the batch's rounds (k_state_mirror's
-// way).
+// way).  (Not a template: defined in st_kernels.hip's translation unit only;
+// st_half.h includes this header with ST_DEVICE_TEMPLATES_ONLY.)
+#ifndef ST_DEVICE_TEMPLATES_ONLY
 __global__ __launch_bounds__(64) void
 k_count_mirror(const uint32_t* __restrict__ d, uint32_t* h)
 {
   if (threadIdx.x == 0)
     __hip_atomic_store(h, *d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // the round split in two launches, for a sharded solve whose all-gather of
@@ -1430,6 +1433,7 @@ k_flat_sum(const T* __restrict__ a, T* __restrict__ part, uint32_t nrows,
 // replaces a device-to-host copy on the stream, a blit launch whose own
 // dispatch gaps cost ~20 us per batch (rocprofv3 trace of the whole solves,
 // profiles/r03_state_mirror_*.log).
+#ifndef ST_DEVICE_TEMPLATES_ONLY // as k_count_mirror
 __global__ __launch_bounds__(64) void
 k_state_mirror(const uint32_t* __restrict__ d, uint32_t* h)
 {
@@ -1437,6 +1441,7 @@ k_state_mirror(const uint32_t* __restrict__ d, uint32_t* h)
   if (i < (uint32_t)(sizeof(st_state) / 4))
     __hip_atomic_store(&h[i], d[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+#endif
 
 // The matrix-free round's second launch (after k_flat<..., MF>): one wave
 // per row sums its pieces in k_parts' order, s_k[r] = Σ / x[r] with

@@ -127,6 +127,19 @@ int launch_mfree_flat(const T* a0, const T* s_prev, T* s_next, const T* v_prev,
                       T* v_cur, T* part, uint32_t nrows, uint32_t ncols,
                       uint32_t row0, T eps, uint32_t k, uint32_t max_itr,
                       uint32_t semantics, st_state* st, hipStream_t stream);
+// the matrix-free round and K0 on a matrix stored in 16 bits (st_half.hip;
+// storage = ST_STORE_F16 / ST_STORE_BF16, fp32 vectors and arithmetic), and
+// the fp32 -> 16-bit rounding that makes such a matrix
+int check_storage(const char* what, int storage);
+int launch_rowsum_half(int storage, const void* a, float* s, uint32_t nrows,
+                       uint32_t ncols, hipStream_t stream);
+int launch_mfree_half(int storage, const void* a0, const float* s_prev,
+                      float* s_next, const float* v_prev, float* v_cur,
+                      uint32_t nrows, uint32_t ncols, uint32_t row0, float eps,
+                      uint32_t k, uint32_t max_itr, uint32_t semantics,
+                      st_state* st, hipStream_t stream);
+int launch_narrow(int storage, const float* in, void* out, uint64_t count,
+                  hipStream_t stream);
 template <typename T>
 int launch_epilogue(const T* s, T* v, uint32_t n, T eps, uint32_t max_itr,
                     uint32_t semantics, st_state* st, hipStream_t stream);

@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "st_internal.h"
@@ -309,13 +310,18 @@ resolve(const st_options* opt, Resolved* r)
 
 // The round loop on a device-resident matrix (transformed in place).
 // flush_matrix: leave the matrix as the every-round loop would (the caller
-// sees it); a private copy (solve_host) skips the deferred loop's last store
+// sees it); a private copy (solve_host) skips the deferred loop's last store.
+// storage != 0 (ST_STORE_F16 / ST_STORE_BF16, T = float): d_mat holds n x n
+// 16-bit elements and is read only - the matrix-free loop with the launchers
+// of st_half.hip for K0 and the round (solve_device_half checks the options)
 template <typename T>
 int64_t
 solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
              T* eigen_val, uint32_t* iter_cnt, const st_options* opt,
-             st_stats* stats, bool flush_matrix = true)
+             st_stats* stats, bool flush_matrix = true, int storage = 0)
 {
+  static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value,
+                "fp32 / fp64 vectors");
   ST_REQUIRE(c, "null queue");
   ST_REQUIRE(d_mat, "null matrix");
   ST_REQUIRE(n > 0, "dim must be > 0");
@@ -346,7 +352,7 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
     if (ensure_trace(c, row_bytes * o.max_itr))
       return -1;
   }
-  const bool mfree = (o.flags & ST_FLAG_MATRIX_FREE) != 0;
+  const bool mfree = storage != 0 || (o.flags & ST_FLAG_MATRIX_FREE) != 0;
   // large matrices: the flat round (k_flat + k_parts)
   const bool flat = !mfree && round_flat_pays(n, n, sizeof(T));
   // the flat round stores the matrix every kDefer rounds (bit-identical
@@ -363,7 +369,7 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   }
   // K0 takes the flat form wherever the flat round pays (the matrix-free
   // loop's too)
-  const bool flat_k0 = round_flat_pays(n, n, sizeof(T));
+  const bool flat_k0 = storage == 0 && round_flat_pays(n, n, sizeof(T));
   if (flat_k0 && ensure_part(c, sizeof(T) * round_flat_scratch(n, n)))
     return -1;
   T* d_part = reinterpret_cast<T*>(c->d_part);
@@ -408,8 +414,13 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
     (void)hipEventRecord(ev[0], s);
   }
   T* const s0 = defer ? ring_s[0] : s_buf[0];
-  if (!single && (flat_k0 ? launch_rowsum_flat<T>(d_mat, s0, d_part, n, n, s)
-                          : launch_rowsum<T>(d_mat, s0, n, n, s))) // K0
+  if (storage != 0) { // K0 on the 16-bit matrix
+    if constexpr (std::is_same<T, float>::value) {
+      if (launch_rowsum_half(storage, d_mat, s0, n, n, s))
+        return -1;
+    }
+  } else if (!single && (flat_k0 ? launch_rowsum_flat<T>(d_mat, s0, d_part, n, n, s)
+                                 : launch_rowsum<T>(d_mat, s0, n, n, s))) // K0
     return -1;
   if (defer && launch_recip<T>(ring_s[0], ring_inv[0], n, s))
     return -1;
@@ -441,7 +452,12 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
         ev.push_back(eb);
         (void)hipEventRecord(ea, s);
       }
-      if (mfree) // launch k+1 evaluates round k
+      if (storage != 0) { // launch k+1 evaluates round k
+        if constexpr (std::is_same<T, float>::value)
+          rc |= launch_mfree_half(storage, d_mat, s_buf[cur], s_buf[cur ^ 1],
+                                  vb[k & 1], vb[(k + 1) & 1], n, n, 0, eps,
+                                  k + 1, o.max_itr, o.semantics, c->d_state, s);
+      } else if (mfree)
         rc |= launch_mfree<T>(d_mat, s_buf[cur], s_buf[cur ^ 1], vb[k & 1],
                               vb[(k + 1) & 1], n, n, 0, eps, k + 1, o.max_itr,
                               o.semantics, c->d_state, s);
@@ -552,6 +568,72 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
     }
   }
   return (int64_t)loop_ms;
+}
+
+// The solve on a device-resident matrix stored in 16 bits (read only):
+// solve_device<float>'s matrix-free loop - gated batches, pinned state
+// mirror, v ping-pong, timing and tracing - with the 16-bit launchers.
+// Everything is checked before anything is enqueued.
+int64_t
+solve_device_half(Context* c, int storage, const void* d_mat, uint32_t n,
+                  float* d_v_out, float* v_host, float* eigen_val,
+                  uint32_t* iter_cnt, const st_options* opt, st_stats* stats)
+{
+  if (check_storage("half solve", storage))
+    return -1;
+  const uint32_t flags = opt ? opt->flags : 0u;
+  constexpr uint32_t kNoHalf =
+    ST_FLAG_ROUND_LOOP | ST_FLAG_WRITE_EVERY_ROUND | ST_FLAG_BATCH_ROUNDS;
+  ST_REQUIRE((flags & kNoHalf) == 0,
+             "half solve: ST_FLAG_ROUND_LOOP, ST_FLAG_WRITE_EVERY_ROUND and "
+             "ST_FLAG_BATCH_ROUNDS are not supported (flags = %u): the matrix "
+             "is read only and every round is one launch", flags);
+  ST_REQUIRE(((uintptr_t)d_mat & 1u) == 0, "half solve: matrix not 2-byte aligned");
+  // the loop never writes through this pointer when storage != 0
+  float* m = static_cast<float*>(const_cast<void*>(d_mat));
+  return solve_device<float>(c, m, n, d_v_out, v_host, eigen_val, iter_cnt, opt,
+                             stats, false, storage);
+}
+
+int64_t
+solve_host_half(Context* c, int storage, const void* mat, uint32_t n,
+                float* eigen_val, float* eigen_vec, uint32_t* iter_cnt,
+                const st_options* opt, st_stats* stats)
+{
+  if (check_storage("half solve", storage))
+    return -1;
+  {
+    const uint32_t flags = opt ? opt->flags : 0u;
+    ST_REQUIRE((flags & (ST_FLAG_ROUND_LOOP | ST_FLAG_WRITE_EVERY_ROUND |
+                         ST_FLAG_BATCH_ROUNDS)) == 0,
+               "half solve: ST_FLAG_ROUND_LOOP, ST_FLAG_WRITE_EVERY_ROUND and "
+               "ST_FLAG_BATCH_ROUNDS are not supported (flags = %u): the matrix "
+               "is read only and every round is one launch", flags);
+    Resolved o;
+    if (resolve<float>(opt, &o))
+      return -1;
+  }
+  ST_REQUIRE(c, "null queue");
+  ST_REQUIRE(mat && eigen_val && eigen_vec && iter_cnt, "null pointer");
+  ST_REQUIRE(n > 0, "dim must be > 0");
+  if (ensure_device(c))
+    return -1;
+  const size_t bytes = 2 * (size_t)n * n;
+  if (ensure_matrix(c, bytes))
+    return -1;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(c->d_mat, mat, bytes, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  if (solve_device_half(c, storage, c->d_mat, n, nullptr, eigen_vec, eigen_val,
+                        iter_cnt, opt, &local) < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
 }
 
 template <typename T>
@@ -1241,6 +1323,30 @@ st_solve_device_f32(void* wq, float* d_mat, unsigned int dim,
   return st::solve_device<float>(st::as_ctx(wq), d_mat, dim, d_eigen_vec,
                                  eigen_vec_host, eigen_val, iter_cnt, opt,
                                  stats);
+}
+
+int64_t
+st_solve_device_half(void* wq, int storage, const void* d_mat, unsigned int dim,
+                     float* d_eigen_vec, float* eigen_vec_host,
+                     float* eigen_val, unsigned int* iter_cnt,
+                     const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_device_half(st::as_ctx(wq), storage, d_mat, dim, d_eigen_vec,
+                               eigen_vec_host, eigen_val, iter_cnt, opt, stats);
+}
+
+int64_t
+max_eigen_value_half_ex(void* wq, int storage, const void* mat,
+                        float* eigen_val, float* eigen_vec, unsigned int dim,
+                        unsigned int* iter_cnt, const st_options* opt,
+                        st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_half(st::as_ctx(wq), storage, mat, dim, eigen_val,
+                             eigen_vec, iter_cnt, opt, stats);
 }
 
 int64_t

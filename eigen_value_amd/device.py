@@ -184,6 +184,67 @@ def mfree_round_flat(mat0, s_prev, s_next, v_prev, v_cur, part, state, row0: int
         "mfree_round_flat")
 
 
+def _storage(t) -> int:
+    """The storage code of a float16 / bfloat16 tensor (ST_STORE_*)."""
+    torch = _torch()
+    if t.dtype == torch.float16:
+        return _lib.ST_STORE_F16
+    if t.dtype == torch.bfloat16:
+        return _lib.ST_STORE_BF16
+    raise TypeError(f"float16/bfloat16 tensor required, got {t.dtype}")
+
+
+def narrow(x, dtype, out=None):
+    """``x`` (float32) rounded to nearest even into a float16 / bfloat16
+    tensor of the same shape (``st_narrow_f32``): how a half matrix is made
+    from the fp32 generators."""
+    torch = _torch()
+    _check_cuda(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"float32 tensor required, got {x.dtype}")
+    assert x.is_contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    _check_cuda(out)
+    assert out.is_contiguous() and out.numel() == x.numel()
+    _lib.check(_lib.load().st_narrow_f32(_storage(out), _ptr(x), _ptr(out), x.numel(),
+                                         _stream(x.device)), "st_narrow_f32")
+    return out
+
+
+def rowsum_half(mat, out=None):
+    """s[r] = Σ_c A[r][c] in float32 for a float16 / bfloat16 ``mat``
+    (``st_rowsum_half``): launch 0 of the half matrix-free scheme."""
+    torch = _torch()
+    _check_cuda(mat)
+    assert mat.is_contiguous() and mat.dim() == 2
+    if out is None:
+        out = torch.empty(mat.shape[0], dtype=torch.float32, device=mat.device)
+    assert out.dtype == torch.float32 and out.numel() >= mat.shape[0]
+    _lib.check(_lib.load().st_rowsum_half(_storage(mat), _ptr(mat), _ptr(out), mat.shape[0],
+                                          mat.shape[1], _stream(mat.device)), "rowsum_half")
+    return out
+
+
+def mfree_round_half(mat0, s_prev, s_next, v_prev, v_cur, state, row0: int = 0,
+                     eps: float = 1e-3, k: int = 1, max_itr: int = _lib.ST_MAX_ITR,
+                     semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Matrix-free launch k >= 1 on a float16 / bfloat16 ``mat0``
+    (``st_mfree_round_half``): mfree_round's contract with float32 vectors;
+    v_cur and the state are bit for bit mfree_round's on the widened matrix."""
+    torch = _torch()
+    _check_cuda(mat0, s_prev, s_next, v_prev, v_cur, state)
+    assert mat0.is_contiguous() and mat0.dim() == 2
+    assert all(t.dtype == torch.float32 for t in (s_prev, s_next, v_prev, v_cur))
+    nrows, ncols = mat0.shape
+    assert s_prev.numel() >= ncols and v_prev.numel() >= ncols and v_cur.numel() >= ncols
+    assert s_next.numel() >= nrows and row0 + nrows <= ncols
+    _lib.check(_lib.load().st_mfree_round_half(
+        _storage(mat0), _ptr(mat0), _ptr(s_prev), _ptr(s_next), _ptr(v_prev), _ptr(v_cur),
+        nrows, ncols, row0, eps, k, max_itr, semantics, _ptr(state),
+        _stream(mat0.device)), "mfree_round_half")
+
+
 def flat_round_pays(nrows: int, ncols: int, dtype) -> bool:
     """Whether the flat round (st_round_flat) is the faster form for a block."""
     torch = _torch()
@@ -436,6 +497,59 @@ class DeviceSolver:
             ctypes.byref(opt), ctypes.byref(stats))
         _lib.check(rc, "st_solve_device")
         return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def solve_half(self, mat, *, eps: Optional[float] = None, max_itr: int = 0,
+                   semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
+                   time_kernels: bool = False, trace_sums: bool = False):
+        """The matrix-free solve of a ``torch.float16`` / ``torch.bfloat16``
+        matrix read where it lies, 2 bytes per element and round
+        (``st_solve_device_half``); vectors, stop test and arithmetic are
+        float32.  Returns (λ: float, v: float32 tensor, iterations: int,
+        stats: dict).
+
+        ``mat`` (a tensor or any DLPack producer, square, on this device) is
+        never written; a non-contiguous ``mat`` is solved as its contiguous
+        copy.  Other dtypes raise ``TypeError`` (``solve`` takes float32 /
+        float64).  ``last_round_sums()`` works after ``trace_sums``."""
+        torch = _torch()
+        if not isinstance(mat, torch.Tensor) and hasattr(mat, "__dlpack__"):
+            mat = torch.from_dlpack(mat)   # any DLPack producer, zero copy
+        storage = _storage(mat)            # TypeError before anything else
+        _check_cuda(mat)
+        if mat.device.index != (self.device.index if self.device.index is not None
+                                else torch.cuda.current_device()):
+            raise ValueError(f"matrix on {mat.device}, solver context on {self.device}")
+        n = mat.shape[0]
+        assert mat.dim() == 2 and mat.shape == (n, n), "must be square"
+        work = mat.contiguous()
+        v = torch.empty(n, dtype=torch.float32, device=mat.device)
+        ev = ctypes.c_float()
+        it = ctypes.c_uint32()
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace_sums else 0))
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
+        stats = _lib.st_stats()
+        self._trace = (n, torch.float32)
+        _lib.check(self.L.st_set_stream(self.q, _stream(mat.device)), "st_set_stream")
+        rc = self.L.st_solve_device_half(
+            self.q, storage, _ptr(work), n, _ptr(v), None, ctypes.byref(ev), ctypes.byref(it),
+            ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(rc, "st_solve_device_half")
+        return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def last_round_times(self):
+        """Per-round kernel times (ms) of the last solve made with
+        ``time_kernels=True`` (``st_last_round_times``; empty otherwise)."""
+        import numpy as np
+        n = _lib.check(self.L.st_last_round_times(self.q, None, 0), "st_last_round_times",
+                       self.L)
+        out = np.zeros(n, dtype=np.float32)
+        if n:
+            _lib.check(self.L.st_last_round_times(self.q, out.ctypes.data, n),
+                       "st_last_round_times", self.L)
+        return out
 
     def solve_batched(self, mats, *, inplace: bool = False, eps: Optional[float] = None,
                       max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,

@@ -186,6 +186,44 @@ class EigenValue:
         vs = [eigen_vecs[int(offs[i]):int(offs[i + 1])] for i in range(b)]
         return eigen_vals, vs, int(ts), iter_cnts
 
+    def similarity_transform_half(self, mat: np.ndarray, storage: Optional[str] = None, *,
+                                  eps: Optional[float] = None, max_itr: int = 0,
+                                  semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
+                                  time_kernels: bool = False, trace_sums: bool = False):
+        """The matrix-free solve of a matrix stored in 16 bits per element
+        (``max_eigen_value_half_ex``): the device reads N^2 * 2 bytes per round
+        and widens them in registers; vectors, stop test and arithmetic are
+        float32.  ``mat`` is a ``np.float16`` array (``storage`` None or
+        ``"f16"``) or, with ``storage="bf16"``, a ``np.uint16`` array of
+        bfloat16 bit patterns (numpy has no bfloat16).
+
+        Returns ``(λ, v, ts_ms, iterations)``, λ and v float32."""
+        m, n = mat.shape
+        assert m == n, "must be square matrix of floating points !"
+        assert storage in (None, "f16", "bf16"), 'storage must be None, "f16" or "bf16" !'
+        if storage == "bf16":
+            assert mat.dtype == np.uint16, \
+                "dtype of a bf16 input matrix must be uint16 (bfloat16 bit patterns) !"
+            code = _lib.ST_STORE_BF16
+        else:
+            assert mat.dtype == np.float16, "dtype of input matrix must be float16 !"
+            code = _lib.ST_STORE_F16
+        mat = np.ascontiguousarray(mat)
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace_sums else 0))
+        self._trace = (n, np.float32)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
+        eigen_val = np.empty(1, dtype=np.float32)
+        eigen_vec = np.empty(n, dtype=np.float32)
+        iter_cnt = np.zeros(1, dtype=np.uint32)
+        ts = self.so_lib.max_eigen_value_half_ex(
+            self.sycl_q, code, mat.ctypes.data, eigen_val.ctypes.data,
+            eigen_vec.ctypes.data, n, iter_cnt.ctypes.data, ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_half_ex", self.so_lib)
+        return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
+
     def last_round_times(self) -> np.ndarray:
         """Per-round kernel times (ms) of the last ``similarity_transform_ex``
         call made with ``time_kernels=True`` (empty otherwise)."""

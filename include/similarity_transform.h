@@ -178,6 +178,38 @@ int64_t st_solve_device_f64(void* wq, double* d_mat, unsigned int dim,
                             double* eigen_val, unsigned int* iter_cnt,
                             const st_options* opt, st_stats* stats);
 
+/* Half-precision STORAGE: the matrix-free solve on a matrix held in 16 bits
+ * per element (N^2 * 2 bytes read per round), widened to fp32 in registers -
+ * exactly, for both formats - with every vector, the stop test, lambda and
+ * all arithmetic in fp32, as st_solve_device_f32 with ST_FLAG_MATRIX_FREE
+ * runs them.  The only difference from solving the widened fp32 matrix is the
+ * association of the row sums (8 columns per lane and load instead of 4).
+ * `storage` codes (the `dtype` parameters of the other calls keep accepting
+ * 0 and 1 only): */
+#define ST_STORE_F16  2   /* IEEE binary16 */
+#define ST_STORE_BF16 3   /* bfloat16      */
+/* d_mat: device pointer, dim x dim row-major 16-bit elements, READ ONLY
+ * (never written, no copy made).  d_eigen_vec / eigen_vec_host / eigen_val /
+ * iter_cnt as st_solve_device_f32 (fp32).  opt: eps < 0 selects ST_EPS_F32;
+ * max_itr, semantics and batch as in st_solve_device_f32;
+ * ST_FLAG_MATRIX_FREE is accepted and implied, ST_FLAG_TIME_KERNELS and
+ * ST_FLAG_TRACE_SUMS work (st_last_round_times; st_last_round_sums returns
+ * float elements); ST_FLAG_ROUND_LOOP, ST_FLAG_WRITE_EVERY_ROUND and
+ * ST_FLAG_BATCH_ROUNDS are errors ("not supported"), as is a storage code
+ * other than 2 or 3 (the message names it) - checked before anything is
+ * enqueued, never a fallback.  Returns loop ms or negative. */
+int64_t st_solve_device_half(void* wq, int storage, const void* d_mat,
+                             unsigned int dim, float* d_eigen_vec,
+                             float* eigen_vec_host, float* eigen_val,
+                             unsigned int* iter_cnt, const st_options* opt,
+                             st_stats* stats);
+/* The host-pointer twin: copies the dim * dim * 2 bytes of `mat` in, solves,
+ * copies out.  Returns h2d + loop ms or negative. */
+int64_t max_eigen_value_half_ex(void* wq, int storage, const void* mat,
+                                float* eigen_val, float* eigen_vec,
+                                unsigned int dim, unsigned int* iter_cnt,
+                                const st_options* opt, st_stats* stats);
+
 /* ---------------------------------------------------------------------- */
 /* 3a. batched solve (many small matrices, one launch)                     */
 /* ---------------------------------------------------------------------- */
@@ -704,6 +736,45 @@ int st_mfree_round_flat_f64(const double* d_mat0, const double* d_s_prev,
                             unsigned int k, unsigned int max_itr,
                             unsigned int semantics, st_state* d_state,
                             void* stream);
+
+/* The matrix-free scheme on a matrix stored in 16 bits (storage =
+ * ST_STORE_F16 / ST_STORE_BF16; what st_solve_device_half runs).  d_mat /
+ * d_mat0: nrows x ncols row-major 16-bit elements, read only, any ncols >= 1;
+ * all vectors fp32.
+ *   st_rowsum_half       d_s[r] = Σ_c A[r][c] (launch 0: s_0)
+ *   st_mfree_round_half  launch k >= 1, the contract of st_mfree_round_f32
+ *     (row0 + nrows <= ncols).  d_v_cur and the whole st_state are bit for
+ *     bit what st_mfree_round_f32 writes for the widened matrix and the same
+ *     arguments; d_s_next sums each row in this kernel's own fixed order: a
+ *     lane takes 8 consecutive columns per 16-byte load (lane t the columns
+ *     8 (t + 256 j) ..+7, j = 0, 1, ...), one fp32 fused multiply-add per
+ *     element in column order, then the 64 lanes' tree and the 4 waves'
+ *     partials in wave order.  16-byte loads when ncols % 8 == 0 and d_mat0,
+ *     d_s_prev and d_v_prev are 16-byte aligned; otherwise the same lanes
+ *     load element-wide (same bits).  Deterministic, no atomics.
+ * st_narrow_f32: d_out[i] = d_in[i] rounded to nearest even in `storage`
+ * (device pointers, count elements): makes a 16-bit matrix from an fp32 one
+ * (e.g. the st_generate_*_f32 inputs). */
+int st_rowsum_half(int storage, const void* d_mat, float* d_s,
+                   unsigned int nrows, unsigned int ncols, void* stream);
+int st_mfree_round_half(int storage, const void* d_mat0, const float* d_s_prev,
+                        float* d_s_next, const float* d_v_prev, float* d_v_cur,
+                        unsigned int nrows, unsigned int ncols,
+                        unsigned int row0, float eps, unsigned int k,
+                        unsigned int max_itr, unsigned int semantics,
+                        st_state* d_state, void* stream);
+int st_narrow_f32(int storage, const float* d_in, void* d_out, uint64_t count,
+                  void* stream);
+/* The launch shape the 16-bit kernels were built with ("rows=8 xvec=0
+ * unroll=2 unroll_mid=1 grid=512 nt_mib=512": rows per group where k_mfree
+ * takes 4, x formed in the sweep, 16-byte chunks in flight per lane and row -
+ * and in the cached 2-row shape -, the workgroup cap, non-temporal loads from
+ * 512 MiB of N^2 * 2 bytes); tools record it next to their numbers.  On
+ * MI355X (tools/bench_half.py, profiles/half_mfree.json, one interleaved
+ * run): 0.0919 / 0.3365 ms per fp16 round at 16384^2 / 32768^2, 5844 / 6382
+ * GB/s, against 0.161 / 0.627 ms for st_mfree_round_f32 on the widened
+ * matrix.  No GPU needed. */
+const char* st_half_shape_desc(void);
 
 /* Round epilogue on the full row-sum vector s[0..n): m = max(0, max s)
  * (find_max, similarity_transform.cpp:154-227), v[i] *= s[i]/m
