@@ -27,9 +27,15 @@
 // zeros, into the same packed registers: the same lanes hold the same
 // numbers, so both paths give the same bits.
 //
-// What does not touch the matrix - the fold of max / stop over s_{k-1}, the v
-// update, the state bookkeeping, the gating on state->end - is k_mfree's code
-// (max and the stop conjunction do not depend on the order of the fold).
+// The fold of max / stop over s_{k-1} is half_group's own (its STATS block):
+// 8 columns per lane and chunk where mfree_group has 4, the chunk's last
+// column paired with s_prev[next chunk] or s_prev[0], zeros past the row on
+// the element-wide path.  max and the stop conjunction do not depend on the
+// order of the fold, so the results are k_mfree<float>'s; which pair and
+// which element it visits is pinned by tests/test_gpu_stats_positions.py
+// (test_mfree_half_round*), position by position.  The rest that does not
+// touch the matrix - the v update, the state bookkeeping, the gating on
+// state->end - is k_mfree's code.
 #pragma once
 
 // wave_sum, ld<>, sweep_tail, kBlock: the templates of st_device.h, without
@@ -154,7 +160,7 @@ half_group(const uint16_t* a0, const float* __restrict__ s_prev,
           for (int i = 0; i < W; i++)
             xs[u][i] = vv[i] * sc[i];
         }
-        if constexpr (STATS) { // as mfree_group, 8 columns per chunk
+        if constexpr (STATS) { // mfree_group's fold, rewritten for W = 8
           const float s0 = s_prev[0];
           const uint32_t nxt = (q + 1) * W;
 #pragma unroll

@@ -19,6 +19,11 @@ answer:
               negative entry, which find_max - it starts at 0 - ignores)
   nan_at      constant with one NaN: the stop test fails, the maximum stands
 
+`positions` lists the boundary positions p for a given chunk width;
+`split_rows` turns an fp32 vector into three pieces that a 16-bit storage
+format holds exactly and that add up to 1024 times the vector, for the
+kernels that sum the rows of a 16-bit matrix themselves.
+
 `eps` is cast to the vector's dtype, as the kernels take it.  The cyclic
 forms need n >= 9 (one_fail / all_pass) or n >= 3 (exact_eps); the open
 forms need p < n - 1.  tests/test_stats_vectors.py checks every
@@ -106,12 +111,15 @@ def nan_at(n: int, p: int, dt) -> np.ndarray:
     return s
 
 
-def positions(n: int, dt, cyclic: bool = True, nrandom: int = 8) -> list:
+def positions(n: int, dt, cyclic: bool = True, nrandom: int = 8, w=None) -> list:
     """Pair positions p to sweep: the vector, lane, wave, workgroup-stride
     (256 lanes), epilogue-block, 8 KB piece, tail and wrap boundaries that
     lie in the valid range (p < n cyclic, p < n - 1 open), and `nrandom`
-    seeded ones."""
-    w = 16 // np.dtype(dt).itemsize
+    seeded ones.  `w` is the number of columns a lane takes per chunk: by
+    default one 16-byte vector of `dt`; 8 for the 16-bit-storage kernels,
+    whose vectors are fp32 but whose chunk is 8 columns (st_half.h)."""
+    if w is None:
+        w = 16 // np.dtype(dt).itemsize
     cls = {0, 1, w - 1, w, 2 * w - 1, 63, 64, 64 * w - 1, 64 * w, 255, 256,
            256 * w - 1, 256 * w, 1023, 1024, 2047, 2048, 4095, 4096,
            n - w - 1, n - w, n - 2, n - 1}
@@ -119,6 +127,36 @@ def positions(n: int, dt, cyclic: bool = True, nrandom: int = 8) -> list:
     rng = np.random.default_rng(1000003 * n + 2 * w + int(cyclic))
     cls |= {int(x) for x in rng.integers(0, last, size=nrandom)}
     return sorted(p for p in cls if 0 <= p < last)
+
+
+def split_rows(S: np.ndarray, storage_bits: int):
+    """1024 * S (fp32) as three fp32 pieces p0, p1, p2, each exactly
+    representable in a 16-bit storage format of `storage_bits` significant
+    bits (8: bfloat16, 11: binary16): p0 is 1024 * S truncated to that many
+    bits, p1 the remainder truncated likewise, p2 what is left (3 * 8 = 24
+    bits cover an fp32 significand).  The pieces are disjoint runs of the
+    bits of 1024 * S, so they - and any two of them - add up exactly in fp32
+    in any order: a matrix row holding them and zeros has the row sum
+    1024 * S bit for bit whatever the kernel's association.  The factor 1024
+    (a power of two: comparisons and quotients are unchanged) lifts the last
+    bit of an S near 1, 2^-23, to 2^-13 - above binary16's smallest normal
+    number 2^-14, so no piece is subnormal.  A NaN goes into p0 alone."""
+    assert storage_bits in (8, 11)
+    S = np.asarray(S)
+    assert S.dtype == np.float32
+    keep = np.uint32(0xffffffff ^ ((1 << (24 - storage_bits)) - 1))
+
+    def trunc(x):
+        return (x.view(np.uint32) & keep).view(np.float32)
+
+    nan = np.isnan(S)
+    t = np.where(nan, np.float32(0), S) * np.float32(1024)
+    p0 = trunc(t)
+    r = t - p0
+    p1 = trunc(r)
+    p2 = r - p1
+    assert np.array_equal(trunc(p2), p2) and np.array_equal(p0 + r, t)
+    return np.where(nan, np.float32(np.nan), p0).astype(np.float32), p1, p2
 
 
 def failing_pairs(s: np.ndarray, eps, cyclic: bool) -> list:

@@ -20,9 +20,25 @@ element-wide path (W = 1), 1032 ... 8200 the vector path; a flat piece is
 1024 columns in every form, so 1032 / 2056 / 4104 / 8200 leave an 8-column
 last piece after 1 / 2 / 4 / 8 whole ones.
 
-Not reachable from here: the non-temporal instantiations (blocks of 2 GiB
-and more; the full-size solve tests run them) and k_stats as a launch of
-its own (the three-launch form is compiled out).
+k_mfree_half (st_half.h) has a fold of its own, half_group's, in which a lane
+takes 8 columns per chunk: its sweeps place the positions by that width
+(sv.positions(..., w=8)), on the 16-byte and the element-wide path, the
+latter also at n % 8 == 0 with a matrix off 16 bytes.
+
+From 1024 rows every launcher groups rows and takes other instantiations:
+k_mfree 2 or 4 rows per group with cached or non-temporal loads, k_mfree_half
+2 (one chunk in flight) or 8, k_round 2.  There every workgroup computes m
+itself and scales its own slice of v with it, the walk is reversed on odd k,
+and workgroup 0's first group - the one whose fold reaches the state - can be
+a remainder row.  The *_grouped sweeps run blocks of 2049 / 4097 / 4099 /
+16389 rows, at both parities of k, and assert the launch shape they mean to
+test: k_mfree_half's non-temporal shape on a 513 MiB block, k_mfree's (which
+the table takes from 512 MiB) on 2049 rows through the tuning build's
+st_set_mfree_shape(3).
+
+Not reachable from here: the non-temporal instantiations of k_round (blocks
+of 1 GiB and more) and k_flat (2 GiB; the full-size solve tests run both) and
+k_stats as a launch of its own (the three-launch form is compiled out).
 """
 import types
 
@@ -66,10 +82,11 @@ def solver():
 _CASES = {}
 
 
-def cases(orc, n, dt, cyclic, only=None):
+def cases(orc, n, dt, cyclic, only=None, w=None):
     """tags, S (case, n), eps, and what the oracle and numpy say of each row:
-    stop and m.  `only`: restrict the positions (the full-size leg)."""
-    key = (n, np.dtype(dt).name, cyclic, None if only is None else tuple(only))
+    stop and m.  `only`: restrict the positions (the full-size leg).  `w`: the
+    columns a lane takes per chunk (sv.positions; None = one 16-byte vector)."""
+    key = (n, np.dtype(dt).name, cyclic, None if only is None else tuple(only), w)
     if key in _CASES:
         return _CASES[key]
     eps, ee = dt(sv.EPS), dt(sv.EXACT_EPS)
@@ -77,12 +94,12 @@ def cases(orc, n, dt, cyclic, only=None):
     # `only`: those positions, where the semantics has a pair / an element there
     pick = (lambda ps: [p for p in sorted(only) if p <= ps[-1]]) if only is not None else (
         lambda ps: ps)
-    for p in pick(sv.positions(n, dt, cyclic)):
+    for p in pick(sv.positions(n, dt, cyclic, w=w)):
         rows += [(("one_fail", p), sv.one_fail(n, p, dt, eps, cyclic), eps, 0),
                  (("all_pass", p), sv.all_pass(n, p, dt, eps, cyclic), eps, 1),
                  (("exact_fail", p), sv.exact_eps(n, p, dt, "fail", cyclic), ee, 0),
                  (("exact_pass", p), sv.exact_eps(n, p, dt, "pass", cyclic), ee, 1)]
-    for p in pick(sv.positions(n, dt, True)):       # an element, not a pair: p = n - 1 too
+    for p in pick(sv.positions(n, dt, True, w=w)):  # an element, not a pair: p = n - 1 too
         rows += [(("max_at", p), sv.max_at(n, p, dt, eps), eps, 1),
                  (("max_decoys", p), sv.max_at(n, p, dt, eps, decoys=True), eps, 0),
                  (("nan_at", p), sv.nan_at(n, p, dt), eps, 0)]
@@ -96,6 +113,7 @@ def cases(orc, n, dt, cyclic, only=None):
     assert c.stop.tolist() == [r[3] for r in rows]
     assert c.stop.tolist() == [int(not sv.failing_pairs(r[1], r[2], cyclic)) for r in rows]
     assert c.m.tolist() == [sv.find_max(r[1]) for r in rows]
+    assert 0 < c.stop.sum() < len(rows)             # stopping and non-stopping jobs
     for a in (c.S, c.eps, c.stop, c.m):
         a.setflags(write=False)
     _CASES[key] = c
@@ -121,27 +139,43 @@ def check(what, got, exp, jobs, c):
                            [(c.tags[jobs[b][0]], jobs[b][1]) for b in bad[:6]])
 
 
-def expect_v(c, ci, v0, full):
+def expect_v(c, ci, v0, full, block=(NROWS, ROW0)):
+    nrows, row0 = block
     with np.errstate(invalid="ignore"):
         upd = v0[None, :] * (c.S[ci] / c.m[ci][:, None])        # cpp:260, in the dtype
     assert upd.dtype == c.dt
     if full:
         return upd
     out = np.tile(v0, (len(ci), 1))
-    out[:, ROW0:ROW0 + NROWS] = upd[:, ROW0:ROW0 + NROWS]
+    out[:, row0:row0 + nrows] = upd[:, row0:row0 + nrows]
     return out
 
 
 def sweep(orc, dt, sem, n, launch, *, full_v=False, flat=False, rk=K, epilogue=False,
-          jobs_of=None, setup=None):
+          jobs_of=None, setup=None, block=(NROWS, ROW0), launch_k=None, w=None, mat=None):
     """Run `launch(x, j, ci, extra)` for every job (case ci, extra), each with
-    its own v and state, read everything back once and compare."""
+    its own v and state, read everything back once and compare.
+
+    block     (nrows, row0) of the matrix block; x.nrows / x.row0
+    launch_k  the launch index k of a matrix-free launch (x.k), which
+              evaluates round rk = k - 1; otherwise `rk` is the round itself
+    w         the chunk width of the positions (cases)
+    mat       x -> the block on the device, for blocks too large to generate
+              on the host (default: the oracle's seeded random rows)"""
     cyclic = sem == _lib.ST_SEM_SYCL
-    c = cases(orc, n, dt, cyclic)
+    nrows, row0 = block
+    assert row0 + nrows <= n
+    if launch_k is not None:
+        rk = launch_k - 1
+    c = cases(orc, n, dt, cyclic, w=w)
     jobs = [(ci, None) for ci in range(len(c.tags))] if jobs_of is None else jobs_of(c)
     v0 = orc.random_matrix(n, 5, dt, nrows=1)[0]
-    x = types.SimpleNamespace(n=n, sem=sem, c=c)
-    x.mat = torch.from_numpy(orc.random_matrix(n, 3, dt, nrows=NROWS, row0=ROW0)).to(DEV)
+    x = types.SimpleNamespace(n=n, sem=sem, c=c, nrows=nrows, row0=row0, k=launch_k)
+    if mat is None:
+        x.mat = torch.from_numpy(orc.random_matrix(n, 3, dt, nrows=nrows, row0=row0)).to(DEV)
+    else:
+        x.mat = mat(x)
+    assert tuple(x.mat.shape) == (nrows, n)
     x.S = torch.tensor(c.S, device=DEV)
     x.v0 = torch.from_numpy(v0).to(DEV)
     x.V = x.v0.repeat(len(jobs), 1)
@@ -171,7 +205,7 @@ def sweep(orc, dt, sem, n, launch, *, full_v=False, flat=False, rk=K, epilogue=F
     if flat:         # the scratch words are left zeroed
         for w in ("arrivals", "max_bits", "fail"):
             check(w, st[w], 0 * stop, jobs, c)
-    check("v", x.V.cpu().numpy(), expect_v(c, ci, v0, full_v), jobs, c)
+    check("v", x.V.cpu().numpy(), expect_v(c, ci, v0, full_v, block), jobs, c)
 
 
 def split_ranges(n, dt, p):
@@ -310,6 +344,243 @@ def test_epilogue(orc, dt, sem, n):
 
 
 # ---------------------------------------------------------------------------
+# the 16-bit-storage round: half_group's own fold, 8 columns per lane and chunk
+# ---------------------------------------------------------------------------
+F32 = np.float32
+HALF_W = 8
+STORAGES = [pytest.param(torch.float16, id="f16"), pytest.param(torch.bfloat16, id="bf16")]
+SEM_PARAMS = [pytest.param(s, id="sycl" if s == _lib.ST_SEM_SYCL else "mainpy") for s in SEMS]
+MIB = 1 << 20
+
+
+def half_desc():
+    return {k: int(v) for k, v in (kv.split("=") for kv in
+                                   _lib.load().st_half_shape_desc().decode().split())}
+
+
+def device_block(x):
+    """The block generated on the device (the library's seeded generator)."""
+    dt = torch.float64 if x.c.dt == np.float64 else torch.float32
+    return dev.generate("random", x.n, dt, nrows=x.nrows, row0=x.row0, seed=3, device=DEV)
+
+
+def half_block(storage, off2=False):
+    """x -> the fp32 block narrowed to `storage` by st_narrow_f32; off2: 2
+    bytes past a 16-byte boundary (test_gpu_half.half_tensor's way)."""
+    def make(x):
+        a = device_block(x)
+        if not off2:
+            h = dev.narrow(a, storage)
+            assert h.data_ptr() % 16 == 0
+            return h
+        flat = torch.empty(a.numel() + 1, dtype=storage, device=DEV)
+        assert flat.data_ptr() % 16 == 0
+        h = flat[1:].view(a.shape)
+        dev.narrow(a, storage, out=h)
+        assert h.data_ptr() % 16 == 2 and h.is_contiguous()
+        return h
+    return make
+
+
+def half_block_of_integers(storage):
+    """x -> small integers generated on the device (exact in both formats), as
+    test_gpu_half.test_exact_in_the_nontemporal_shape makes its matrix."""
+    def make(x):
+        g = torch.Generator(device=DEV).manual_seed(5)
+        return torch.randint(1, 9, (x.nrows, x.n), device=DEV, generator=g,
+                             dtype=torch.int32).to(storage)
+    return make
+
+
+def half_launch(x, j, ci, _):
+    dev.mfree_round_half(x.mat, x.S[ci], x.s_next, x.v0, x.V[j], x.ST[j], row0=x.row0,
+                         eps=x.eps[ci], k=x.k, max_itr=MAX_ITR, semantics=x.sem)
+
+
+def vector_path(x):
+    """What mfree_half's vec_ok reads (st_half.hip)."""
+    return (x.n % HALF_W == 0 and x.mat.data_ptr() % 16 == 0 and x.v0.data_ptr() % 16 == 0
+            and all(x.S[ci].data_ptr() % 16 == 0 for ci in range(x.S.shape[0])))
+
+
+@pytest.mark.parametrize("n", sv.SIZES)
+@pytest.mark.parametrize("sem", SEM_PARAMS)
+@pytest.mark.parametrize("storage", STORAGES)
+def test_mfree_half_round(orc, storage, sem, n):
+    """k_mfree_half, 1 row per group: the STATS block of half_group at every
+    chunk (7|8), wave (511|512), workgroup-pass (2047|2048) and unrolled-stride
+    (4095|4096) boundary, in sweep_tail, in the ragged last chunk and at the
+    wrap.  n = 9, 257, 1031: the element-wide path (zeros past the row); the
+    others the 16-byte path."""
+    def setup(x):
+        assert vector_path(x) == (n % HALF_W == 0)
+    sweep(orc, F32, sem, n, half_launch, full_v=True, launch_k=1, w=HALF_W,
+          mat=half_block(storage), setup=setup)
+
+
+@pytest.mark.parametrize("sem", SEM_PARAMS)
+@pytest.mark.parametrize("storage", STORAGES)
+def test_mfree_half_round_misaligned_matrix(orc, storage, sem):
+    """n = 1032 with the matrix 2 bytes past a 16-byte boundary: the
+    element-wide path at n % 8 == 0, where no column lies past the row."""
+    def setup(x):
+        assert not vector_path(x) and x.mat.data_ptr() % 16 == 2
+    sweep(orc, F32, sem, 1032, half_launch, full_v=True, launch_k=1, w=HALF_W,
+          mat=half_block(storage, off2=True), setup=setup)
+
+
+def half_grouped_shape(nrows, ncols):
+    """(rows per group, chunks in flight, non-temporal, groups + remainder
+    rows, workgroups, groups of workgroup 0) of mfree_half's launch - from the
+    library's own description of its table and the block's bytes, so that a
+    retuned table fails the shape assertions below instead of moving the
+    sweeps to another instantiation unnoticed."""
+    d = half_desc()
+    b = nrows * ncols * 2
+    assert nrows >= 1024 and d["xvec"] == 0
+    if b >= d["nt_mib"] * MIB:
+        rows, u, nt = d["rows"], d["unroll"], True
+    elif 64 * MIB < b < 280 * MIB:
+        rows, u, nt = 2, d["unroll_mid"], False
+    else:
+        rows, u, nt = d["rows"], d["unroll"], False
+    ng = nrows // rows + nrows % rows
+    grid = min(ng, d["grid"])
+    return rows, u, nt, (nrows // rows, nrows % rows), grid, (ng - 1) // grid + 1
+
+
+HALF_GROUPED = {
+    # 32 MiB: 8 rows per group, 512 groups + 1 remainder row on 512 workgroups:
+    # workgroup 0 holds group 0 and the remainder row, and starts on the
+    # remainder row (the 1-row instantiation folds the stats) where the walk
+    # is reversed, k = 1, on group 0 (the 8-row instantiation) at k = 2
+    "rows8": ((4097, 4104, 3), (8, 2, False, (512, 1), 512, 2)),
+    # 64.1 MiB: the cached 2-row shape, one chunk in flight, 5 groups per workgroup
+    "rows2": ((4099, 8200, 101), (2, 1, False, (2049, 1), 512, 5)),
+    # 513 MiB: non-temporal, 8 rows per group
+    "nontemporal": ((16389, 16400, 5), (8, 2, True, (2048, 5), 512, 5)),
+}
+
+
+def half_grouped(orc, storage, sem, name, k):
+    (nrows, n, row0), shape = HALF_GROUPED[name]
+    assert half_grouped_shape(nrows, n) == shape, (name, half_desc())
+
+    def setup(x):
+        assert vector_path(x)
+    big = nrows * n * 2 >= 256 * MIB
+    sweep(orc, F32, sem, n, half_launch, full_v=True, launch_k=k, w=HALF_W, block=(nrows, row0),
+          mat=half_block_of_integers(storage) if big else half_block(storage), setup=setup)
+
+
+@pytest.mark.parametrize("k", [1, 2])
+@pytest.mark.parametrize("sem", SEM_PARAMS)
+@pytest.mark.parametrize("storage", STORAGES)
+@pytest.mark.parametrize("name", ["rows8", "rows2"])
+def test_mfree_half_round_grouped(orc, name, storage, sem, k):
+    """k_mfree_half's grouped launches (from 1024 rows): every workgroup folds
+    the stats in its first group and scales its own slice of v_cur with its
+    own m; the walk is reversed on odd k."""
+    half_grouped(orc, storage, sem, name, k)
+
+
+@pytest.mark.parametrize("k", [1, 2])
+@pytest.mark.parametrize("sem", SEM_PARAMS)
+def test_mfree_half_round_nontemporal(orc, sem, k):
+    """The same in the non-temporal shape (a 513 MiB block, bf16)."""
+    half_grouped(orc, torch.bfloat16, sem, "nontemporal", k)
+
+
+# ---------------------------------------------------------------------------
+# the grouped launches of k_mfree and k_round (from 1024 rows)
+# ---------------------------------------------------------------------------
+GROUPED = (2049, 3)          # 2049 = 4 * 512 + 1 = 2 * 1024 + 1: a remainder row either way
+GROUPED_PARAMS = [pytest.param(dt, sem, id=f"{np.dtype(dt).name}-{'sycl' if sem == 0 else 'mainpy'}")
+                  for dt in (np.float64, np.float32) for sem in SEMS]
+
+
+def policy(L, dt, nrows, ncols, form):
+    """st_launch_policy_query of the library `L` (the tuning build answers
+    with its own, overridden, table)."""
+    import ctypes
+    out = _lib.st_launch_policy()
+    _lib.check(L.st_launch_policy_query(1 if dt == np.float64 else 0, nrows, ncols, form, 0,
+                                        ctypes.byref(out)), "st_launch_policy_query", L)
+    return _lib.KERNEL_NAMES[out.kernel], out.rows, bool(out.load_nt), out.grid
+
+
+def mfree_launch_through(L):
+    """dev.mfree_round through the library `L`."""
+    def launch(x, j, ci, _):
+        sfx = "f64" if x.c.dt == np.float64 else "f32"
+        s, v = x.S[ci], x.V[j]
+        assert x.mat.is_contiguous() and s.numel() >= x.n and v.numel() >= x.n
+        assert x.s_next.numel() >= x.nrows and x.row0 + x.nrows <= x.n
+        _lib.check(getattr(L, f"st_mfree_round_{sfx}")(
+            x.mat.data_ptr(), s.data_ptr(), x.s_next.data_ptr(), x.v0.data_ptr(), v.data_ptr(),
+            x.nrows, x.n, x.row0, x.eps[ci], x.k, MAX_ITR, x.sem, x.ST[j].data_ptr(),
+            torch.cuda.current_stream(DEV).cuda_stream), "mfree_round", L)
+    return launch
+
+
+@pytest.mark.parametrize("k", [1, 2])
+@pytest.mark.parametrize("n", [2056, 2059])
+@pytest.mark.parametrize("dt,sem", GROUPED_PARAMS)
+def test_mfree_round_grouped(orc, dt, sem, n, k):
+    """k_mfree on 2049 rows: 4 rows per group, 512 groups + 1 remainder row on
+    512 workgroups.  k = 1 (reversed walk): workgroup 0 folds the stats in the
+    1-row remainder instantiation; k = 2: in the 4-row one.  n = 2059: the
+    element-wide path."""
+    nrows, row0 = GROUPED
+    L = _lib.load()
+    # (the query takes whole 16-byte chunks per row; the table reads rows and bytes)
+    assert policy(L, dt, nrows, 2056, _lib.ST_FORM_MFREE) == ("k_mfree", 4, False, 512)
+    assert policy(L, dt, nrows, 2064, _lib.ST_FORM_MFREE) == ("k_mfree", 4, False, 512)
+    sweep(orc, dt, sem, n, mfree_launch_through(L), full_v=True, launch_k=k, block=GROUPED,
+          mat=device_block)
+
+
+@pytest.mark.parametrize("k", [1, 2])
+@pytest.mark.parametrize("shape,rows,nt", [(1, 2, False), (2, 4, False), (3, 4, True)],
+                         ids=["cached2", "cached4", "nontemporal4"])
+@pytest.mark.parametrize("dt,sem", GROUPED_PARAMS)
+def test_mfree_round_grouped_shapes(orc, dt, sem, shape, rows, nt, k):
+    """The other instantiations of k_mfree - 2 rows per group (1024 groups +
+    1 row: 3 groups per workgroup), and 4 rows with non-temporal loads, which
+    the table takes from 512 MiB - on the same 2049 x 2056 block, through the
+    tuning build (st_set_mfree_shape; its kernels are the product's)."""
+    nrows, row0 = GROUPED
+    n = 2056
+    L = _lib.load_tuning()
+    saved = L.st_set_mfree_shape(0)
+    try:
+        assert L.st_set_mfree_shape(shape) >= 0
+        assert policy(L, dt, nrows, n, _lib.ST_FORM_MFREE) == ("k_mfree", rows, nt, 512)
+        sweep(orc, dt, sem, n, mfree_launch_through(L), full_v=True, launch_k=k, block=GROUPED,
+              mat=device_block)
+    finally:
+        L.st_set_mfree_shape(saved)
+
+
+@pytest.mark.parametrize("k", [2, 3])
+@pytest.mark.parametrize("dt,sem", GROUPED_PARAMS)
+def test_fused_round_grouped(orc, dt, sem, k):
+    """k_round on 2049 x 2056: 2 rows per group, 1024 groups + 1 remainder row
+    (fp64, 32.1 MiB: on 512 workgroups; fp32 on 1024), forward at k = 2 and
+    reversed at k = 3."""
+    nrows, row0 = GROUPED
+    n = 2056
+    kernel, rows, nt, grid = policy(_lib.load(), dt, nrows, n, _lib.ST_FORM_ROUND)
+    assert (kernel, rows, nt) == ("k_round", 2, False)
+    assert grid == (512 if dt == np.float64 else 1024)
+
+    def launch(x, j, ci, _):
+        dev.fused_round(x.mat, x.S[ci], x.s_next, x.V[j], x.ST[j], row0=row0, eps=x.eps[ci],
+                        k=k, max_itr=MAX_ITR, semantics=sem)
+    sweep(orc, dt, sem, n, launch, rk=k, block=GROUPED, mat=device_block)
+
+
+# ---------------------------------------------------------------------------
 # 8 - 11: the kernels that derive s_k themselves.  A = diag(d), max_itr = 1: a
 # row's sum is exactly d[r] in any summation order (the rest are zeros), so
 # round 0's stop test runs on s_0 = d, v_0 = 1 * (d / m) = d / m
@@ -366,6 +637,65 @@ def test_solve_round_loop_sizes(solver, orc, dt, n, sem):
     solve_each(solver, orc, dt, sem, n)
 
 
+@pytest.mark.parametrize("sem", SEMS)
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+@pytest.mark.parametrize("n", [1032, 2056])
+def test_solve_matrix_free_loop_sizes(solver, orc, dt, n, sem):
+    """The same sizes through the matrix-free loop: K0 and k_mfree at a
+    grouped launch shape (from 1024 rows), as the solve launches them."""
+    assert _lib.launch_policy("f64" if dt == np.float64 else "f32", n, n,
+                              _lib.ST_FORM_MFREE)["rows"] == 4
+    solve_each(solver, orc, dt, sem, n, matrix_free=True)
+
+
+@pytest.mark.parametrize("n", [9, 257, 1032, 2056])
+@pytest.mark.parametrize("sem", SEM_PARAMS)
+@pytest.mark.parametrize("storage,bits", [pytest.param(torch.float16, 11, id="f16"),
+                                          pytest.param(torch.bfloat16, 8, id="bf16")])
+def test_solve_half(solver, orc, storage, bits, sem, n):
+    """solve_half (k_rowsum_half, then k_mfree_half as the solve launches it;
+    8 rows per group from 1024 rows).  No 16-bit format holds these s, so row
+    r of the matrix holds the three pieces of 1024 * s[r] (sv.split_rows, each
+    exact in the storage format) at columns r, r + 1, r + 2 (mod n) and zeros:
+    K0's row sum is 1024 * s[r] bit for bit in any order, and with eps scaled
+    by the same power of two every comparison, s / m and the stop decision
+    are those of s."""
+    cyclic = sem == _lib.ST_SEM_SYCL
+    c = cases(orc, n, F32, cyclic, w=HALF_W)
+    ncase = len(c.tags)
+    P = np.stack(sv.split_rows(c.S, bits), axis=1)              # (case, 3, n)
+    Hd = dev.narrow(torch.from_numpy(P).to(DEV), storage)       # st_narrow_f32
+    assert same(Hd.cpu().float().numpy(), P).all()              # the narrowing is exact
+    h = torch.zeros((n, n), dtype=storage, device=DEV)
+    # piece d of row r at column (r + d) % n: the diagonals 0, 1, 2 and their
+    # wrapped ends (n - 1, 0), (n - 2, 0), (n - 1, 1); the same 3 n slots each time
+    slots = [(h.diagonal(0), 0, 0, n), (h.diagonal(1), 1, 0, n - 1),
+             (h.diagonal(1 - n), 1, n - 1, n), (h.diagonal(2), 2, 0, n - 2),
+             (h.diagonal(2 - n), 2, n - 2, n)]
+    assert sum(view.numel() for view, *_ in slots) == 3 * n
+    lam, its, conv, vs = [], [], [], []
+    for ci in range(ncase):
+        for view, d, lo, hi in slots:
+            view.copy_(Hd[ci, d, lo:hi])
+        l, v, it, st = solver.solve_half(h, eps=1024.0 * float(c.eps[ci]), max_itr=1,
+                                         semantics=sem)
+        lam.append(l), its.append(it), conv.append(st["converged"]), vs.append(v)
+    last = h.cpu().float().numpy()                              # the last case's matrix
+    r = np.arange(n)
+    for d in range(3):
+        assert same(last[r, (r + d) % n], P[ncase - 1, d]).all()
+        last[r, (r + d) % n] = 0
+    assert not last.any()                                       # zeros elsewhere
+    jobs = [(ci, None) for ci in range(ncase)]
+    stop, iters, v = expect_solve(c, np.arange(ncase))
+    check("converged", np.array(conv), stop, jobs, c)
+    check("iterations", np.array(its), iters, jobs, c)
+    check("lambda", np.array(lam, dtype=np.float64),
+          (np.float32(1024) * c.S[:, 0]).astype(np.float64), jobs, c)
+    torch.cuda.synchronize()
+    check("v", torch.stack(vs).cpu().numpy(), v, jobs, c)
+
+
 def batched(solver, orc, dt, sem, n, **kw):
     """One diagonal matrix per case, stacked: entry b must stop, or not, on
     its own (one batch per eps: the batch shares it)."""
@@ -401,6 +731,55 @@ def test_solve_batched(solver, orc, dt, n, sem):
 def test_solve_batched_round_loop(solver, orc, dt, n, sem, batch):
     """k_round_batched: one launch per round for the whole batch."""
     batched(solver, orc, dt, sem, n, round_loop=True, batch=batch)
+
+
+VDIMS = {np.float64: [9, 63, 64, 127, 128], np.float32: [9, 63, 64, 127, 128, 255, 256]}
+
+
+@pytest.mark.parametrize("misaligned", [False, True], ids=["aligned", "off1"])
+@pytest.mark.parametrize("sem", SEM_PARAMS)
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+def test_solve_vbatched(solver, orc, dt, sem, misaligned):
+    """k_solve_vbatched: diagonal matrices of every dim in ONE call per eps
+    (each workgroup-shape class one launch, dims interleaved), every entry
+    with a stop decision of its own; once on 16-byte aligned bases and once
+    with every base one element past a 16-byte boundary (the layout of
+    test_gpu_vbatched.test_misaligned_base_changes_no_bit), where the kernel
+    takes its element-wide loads."""
+    cyclic = sem == _lib.ST_SEM_SYCL
+    item = np.dtype(dt).itemsize
+    per16 = 16 // item
+    cs = {n: cases(orc, n, dt, cyclic) for n in VDIMS[dt]}
+    Sd = {n: torch.tensor(c.S, device=DEV) for n, c in cs.items()}
+    for e in np.unique(np.concatenate([c.eps for c in cs.values()])):
+        # interleave the dims: entry order by case index, then dim
+        entries = sorted((int(ci), n) for n, c in cs.items() for ci in np.nonzero(c.eps == e)[0])
+        offs, total = [], int(misaligned)
+        for _, n in entries:
+            offs.append(total)
+            total += -(-n * n // per16) * per16 + per16        # keeps every base's alignment
+        buf = torch.zeros(total, dtype=TD[dt], device=DEV)
+        assert buf.data_ptr() % 16 == 0
+        work = [buf[o:o + n * n].view(n, n) for o, (_, n) in zip(offs, entries)]
+        for w_, (ci, n) in zip(work, entries):
+            assert w_.data_ptr() % 16 == (item if misaligned else 0) and w_.is_contiguous()
+            w_.diagonal().copy_(Sd[n][ci])
+        lam, vs, it, st = solver.solve_vbatched(work, inplace=True, eps=float(e), max_itr=1,
+                                                semantics=sem)
+        assert st["converged"] == 0 and st["rounds"] == 1
+        torch.cuda.synchronize()
+        conv, lam, it = st["converged_each"], lam.numpy(), it.numpy()
+        for n, c in cs.items():
+            sel = [b for b, (_, m) in enumerate(entries) if m == n]
+            idx = np.array([entries[b][0] for b in sel])
+            jobs = [(int(ci), None) for ci in idx]
+            stop, iters, vexp = expect_solve(c, idx)
+            assert 0 < stop.sum() < len(idx)                   # both kinds at every dim
+            check("converged_each", conv[sel], stop, jobs, c)
+            check("iterations", it[sel], iters, jobs, c)
+            check("lambda", lam[sel].astype(np.float64), c.S[idx, 0].astype(np.float64), jobs, c)
+            assert all(vs[b].shape == (n,) for b in sel)
+            check("v", torch.stack([vs[b] for b in sel]).cpu().numpy(), vexp, jobs, c)
 
 
 @pytest.mark.parametrize("sem", SEMS)
