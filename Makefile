@@ -8,7 +8,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -Wall -Wextra -Wno-unused-parameter -Iinclude -Ieigen_value_amd/csrc
 SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hip \
             eigen_value_amd/csrc/st_multi.hip eigen_value_amd/csrc/st_rendezvous.hip \
-            eigen_value_amd/csrc/st_half.hip
+            eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip
 OBJ      := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
@@ -18,7 +18,8 @@ TUNING_OBJ := build/st_kernels_tuning.o $(filter-out build/st_kernels.o,$(OBJ))
 LIB_TUNING := eigen_value_amd/lib/libsimilarity_transform_tuning.so
 HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/csrc/st_internal.h \
             eigen_value_amd/csrc/st_device.h eigen_value_amd/csrc/st_rendezvous.h \
-            eigen_value_amd/csrc/st_half.h
+            eigen_value_amd/csrc/st_half.h eigen_value_amd/csrc/st_csr.h \
+            eigen_value_amd/csrc/st_csr_host.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 

@@ -306,6 +306,27 @@ def _declare(L: ctypes.CDLL) -> None:
     L.max_eigen_value_half_ex.restype = i64
     L.st_half_shape_desc.argtypes = []
     L.st_half_shape_desc.restype = ctypes.c_char_p
+    # sparse (CSR) solve
+    L.st_csr_class_limits.argtypes = [i32, P, P, i32]
+    L.st_csr_class_limits.restype = i32
+    L.st_csr_plan.argtypes = [P, u32, P, P]
+    L.st_csr_plan.restype = i32
+    L.st_csr_shape_desc.argtypes = []
+    L.st_csr_shape_desc.restype = ctypes.c_char_p
+    L.st_csr_create.argtypes = [P, i32, u32, u64, P, P, P, ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_create.restype = i32
+    L.st_csr_destroy.argtypes = [P]
+    L.st_csr_destroy.restype = i32
+    L.st_csr_get_plan.argtypes = [P, P, P]
+    L.st_csr_get_plan.restype = i32
+    L.st_solve_csr.argtypes = [P, P, P, P, P, P, P, P]
+    L.st_solve_csr.restype = i64
+    L.max_eigen_value_csr_ex.argtypes = [P, i32, u32, u64, P, P, P, P, P, P, P, P]
+    L.max_eigen_value_csr_ex.restype = i64
+    L.st_csr_rowsum.argtypes = [P, P, P]
+    L.st_csr_rowsum.restype = i32
+    L.st_csr_mfree_round.argtypes = [P, P, P, P, P, P, f64, u32, u32, u32, P, P]
+    L.st_csr_mfree_round.restype = i32
 
 
 def batch_rounds_flag(round_loop, n: int, dtype_code: int) -> int:
@@ -340,6 +361,41 @@ def vbatched_plan(dims, dtype_code: int, L: Optional[ctypes.CDLL] = None):
     first = np.zeros(ST_VBATCH_CLASSES + 1, dtype=np.uint32)
     used = check(L.st_vbatched_plan(dtype_code, dims.ctypes.data, len(dims), order.ctypes.data,
                                     first.ctypes.data), "st_vbatched_plan", L)
+    return order, first, used
+
+
+ST_CSR_CLASSES = 4
+
+
+def csr_class_limits(dtype_code: int = DTYPE_F32, L: Optional[ctypes.CDLL] = None):
+    """The row-class table of the CSR kernels (st_csr_class_limits; no GPU):
+    ``(nnz_max, lanes)``, two uint32 arrays[ST_CSR_CLASSES] - a row of nnz
+    entries belongs to the first class with nnz <= nnz_max and is shared by
+    that class's lanes."""
+    import numpy as np
+    L = L or load()
+    nnz_max = np.zeros(ST_CSR_CLASSES, dtype=np.uint32)
+    lanes = np.zeros(ST_CSR_CLASSES, dtype=np.uint32)
+    got = check(L.st_csr_class_limits(dtype_code, nnz_max.ctypes.data, lanes.ctypes.data,
+                                      ST_CSR_CLASSES), "st_csr_class_limits", L)
+    assert got == ST_CSR_CLASSES
+    return nnz_max, lanes
+
+
+def csr_plan(row_ptr, L: Optional[ctypes.CDLL] = None):
+    """The plan of a host ``row_ptr`` (st_csr_plan; no GPU): ``(order,
+    class_first, used)`` - the row indices sorted by class (row order kept
+    within a class) as a uint32 array[n], the class starts (uint32
+    array[ST_CSR_CLASSES + 1]) and the number of non-empty classes.  Raises
+    EigenValueError naming the row for an empty row or a decreasing row_ptr."""
+    import numpy as np
+    L = L or load()
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    n = len(row_ptr) - 1
+    order = np.zeros(max(n, 0), dtype=np.uint32)
+    first = np.zeros(ST_CSR_CLASSES + 1, dtype=np.uint32)
+    used = check(L.st_csr_plan(row_ptr.ctypes.data, max(n, 0), order.ctypes.data,
+                               first.ctypes.data), "st_csr_plan", L)
     return order, first, used
 
 

@@ -1,0 +1,162 @@
+// st_csr_host.h — the host side of the sparse (CSR) solve that needs no GPU:
+// the row-class table, the plan (rows sorted by class) and the validation of
+// a host CSR matrix.  Plain C++ without any HIP, so that it also compiles
+// into a stand-alone program (tests/cpp/csr_sanitize.cpp, run under the host
+// sanitizers).  Included by st_csr.hip; not a public header.
+//
+// Every function returns 0 (or a count) on success and -1 on failure with
+// the reason written to msg[cap].
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+namespace st {
+namespace csr {
+
+// Row classes: a row of nnz entries belongs to the first class c with
+// nnz <= kNnzMax[c], and kLanes[c] lanes share it (4 and 16: part of a wave,
+// 64: one wave, 256: one workgroup).  The kernels (st_csr.h), the plan and
+// st_csr_class_limits all read this one table.
+constexpr int kClasses = 4;
+constexpr uint32_t kLanes[kClasses] = { 4u, 16u, 64u, 256u };
+constexpr uint32_t kNnzMax[kClasses] = { 16u, 128u, 2048u, 0xffffffffu };
+constexpr uint32_t kBlock = 256; // lanes of a workgroup
+// launch shape (no effect on any result): rows the lanes of a row take side by
+// side, and entries of each row in flight per lane; a workgroup of class c
+// holds kRows[c] * 256 / kLanes[c] rows
+constexpr uint32_t kRows[kClasses] = { 8u, 4u, 2u, 1u };
+constexpr uint32_t kUnroll[kClasses] = { 1u, 2u, 4u, 8u };
+
+// the class of a row of `len` > 0 entries
+inline int
+row_class(uint64_t len)
+{
+  for (int c = 0; c < kClasses - 1; c++)
+    if (len <= kNnzMax[c])
+      return c;
+  return kClasses - 1;
+}
+
+// row_ptr on its own, row by row: row_ptr[0] == 0, strictly increasing (an
+// empty row would divide by zero), row_ptr[n] == nnz when check_nnz.  The
+// device check (k_csr_check_ptr) applies the same predicate per row and
+// reports the lowest offending row through describe_row.
+inline bool
+row_bad(uint32_t r, int64_t a, int64_t b, uint32_t n, bool check_nnz,
+        uint64_t nnz)
+{
+  return (r == 0 && a != 0) || b <= a ||
+         (check_nnz && r == n - 1 && (uint64_t)b != nnz);
+}
+
+// the message for row r with row_ptr[r] = a, row_ptr[r + 1] = b
+inline void
+describe_row(uint32_t r, int64_t a, int64_t b, uint32_t n, uint64_t nnz,
+             char* msg, size_t cap)
+{
+  if (r == 0 && a != 0)
+    snprintf(msg, cap, "csr: row_ptr[0] must be 0, got %lld (row 0)",
+             (long long)a);
+  else if (b < a)
+    snprintf(msg, cap,
+             "csr: row_ptr decreases at row %u (row_ptr[%u] = %lld, "
+             "row_ptr[%u] = %lld)", r, r, (long long)a, r + 1, (long long)b);
+  else if (b == a)
+    snprintf(msg, cap,
+             "csr: row %u is empty (row_ptr[%u] = row_ptr[%u] = %lld): its "
+             "row sum would be divided by zero", r, r, r + 1, (long long)a);
+  else
+    snprintf(msg, cap, "csr: row_ptr[n] must be nnz = %llu, got %lld (row %u)",
+             (unsigned long long)nnz, (long long)b, n - 1);
+}
+
+inline int
+check_row_ptr(const int64_t* row_ptr, uint32_t n, bool check_nnz, uint64_t nnz,
+              char* msg, size_t cap)
+{
+  for (uint32_t r = 0; r < n; r++)
+    if (row_bad(r, row_ptr[r], row_ptr[r + 1], n, check_nnz, nnz)) {
+      describe_row(r, row_ptr[r], row_ptr[r + 1], n, nnz, msg, cap);
+      return -1;
+    }
+  return 0;
+}
+
+// every col_idx[e], e in [0, nnz), inside [0, n); call only after
+// check_row_ptr passed (the row of the offending entry is looked up in it)
+inline int
+check_col_idx(const int64_t* row_ptr, const int32_t* col_idx, uint32_t n,
+              uint64_t nnz, char* msg, size_t cap)
+{
+  for (uint64_t e = 0; e < nnz; e++) {
+    const int32_t c = col_idx[e];
+    if (c < 0 || (uint32_t)c >= n) {
+      uint32_t lo = 0, hi = n; // the row r with row_ptr[r] <= e < row_ptr[r+1]
+      while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if ((uint64_t)row_ptr[mid] <= e)
+          lo = mid;
+        else
+          hi = mid;
+      }
+      snprintf(msg, cap,
+               "csr: column index %d of entry %llu (row %u) is outside [0, %u)",
+               c, (unsigned long long)e, lo, n);
+      return -1;
+    }
+  }
+  return 0;
+}
+
+// The plan: order_out[n] = the row indices sorted by class, row order kept
+// within a class; class_first[kClasses + 1] = where each class starts.
+// Returns the number of non-empty classes.
+inline int
+plan(const int64_t* row_ptr, uint32_t n, uint32_t* order_out,
+     uint32_t* class_first, char* msg, size_t cap)
+{
+  if (check_row_ptr(row_ptr, n, false, 0, msg, cap))
+    return -1;
+  uint32_t count[kClasses] = { 0, 0, 0, 0 };
+  for (uint32_t r = 0; r < n; r++)
+    count[row_class((uint64_t)(row_ptr[r + 1] - row_ptr[r]))]++;
+  uint32_t at[kClasses];
+  int used = 0;
+  class_first[0] = 0;
+  for (int c = 0; c < kClasses; c++) {
+    at[c] = class_first[c];
+    class_first[c + 1] = class_first[c] + count[c];
+    used += count[c] != 0;
+  }
+  for (uint32_t r = 0; r < n; r++)
+    order_out[at[row_class((uint64_t)(row_ptr[r + 1] - row_ptr[r]))]++] = r;
+  return used;
+}
+
+// a whole host matrix, in the order the device check runs: the arguments,
+// row_ptr on its own, then the column indices
+inline int
+check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
+           const int32_t* col_idx, const void* vals, char* msg, size_t cap)
+{
+  if (dtype != 0 && dtype != 1) {
+    snprintf(msg, cap, "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+    return -1;
+  }
+  if (n == 0 || n >= 0x80000000u) {
+    snprintf(msg, cap, "csr: n must be in [1, 2^31), got %u", n);
+    return -1;
+  }
+  if (!row_ptr || !col_idx || !vals) {
+    snprintf(msg, cap, "csr: null row_ptr / col_idx / vals");
+    return -1;
+  }
+  if (check_row_ptr(row_ptr, n, true, nnz, msg, cap))
+    return -1;
+  return check_col_idx(row_ptr, col_idx, n, nnz, msg, cap);
+}
+
+} // namespace csr
+} // namespace st

@@ -140,6 +140,40 @@ int launch_mfree_half(int storage, const void* a0, const float* s_prev,
                       st_state* st, hipStream_t stream);
 int launch_narrow(int storage, const float* in, void* out, uint64_t count,
                   hipStream_t stream);
+// the sparse (CSR) solve (st_csr.hip): a validated matrix with its plan.
+// The three arrays stay the caller's; order is the handle's own.
+struct CsrHandle
+{
+  uint32_t magic; // kCsrMagic while alive
+  int dtype;      // 0 = f32, 1 = f64
+  int device;
+  uint32_t n;
+  uint64_t nnz;
+  const int64_t* row_ptr;
+  const int32_t* col_idx;
+  const void* vals;
+  uint32_t* d_order;     // [n] row indices sorted by class
+  uint32_t row_first[5]; // class starts in d_order
+  uint32_t blk_first[5]; // class starts in the launch's workgroup range
+};
+constexpr uint32_t kCsrMagic = 0x43535231u;
+// what is checked on the host before anything is enqueued: the flags of a
+// CSR solve, and a host-resident matrix (dtype, n, row_ptr, then col_idx)
+int csr_check_flags(const st_options* opt);
+int csr_check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
+                   const int32_t* col_idx, const void* vals);
+// validates on the device (row_ptr first, col_idx only after it passed),
+// builds the plan; synchronises `stream`
+int csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
+               const int32_t* d_col_idx, const void* d_vals, hipStream_t stream,
+               CsrHandle** out);
+int csr_destroy(CsrHandle* h);
+const CsrHandle* as_csr(const void* p, const char* what); // null + error if not one
+int launch_csr_rowsum(const CsrHandle* h, void* s, hipStream_t stream);
+int launch_csr_round(const CsrHandle* h, const void* s_prev, void* s_next,
+                     const void* v_prev, void* v_cur, void* x, double eps,
+                     uint32_t k, uint32_t max_itr, uint32_t semantics,
+                     st_state* st, hipStream_t stream);
 template <typename T>
 int launch_epilogue(const T* s, T* v, uint32_t n, T eps, uint32_t max_itr,
                     uint32_t semantics, st_state* st, hipStream_t stream);

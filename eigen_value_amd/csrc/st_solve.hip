@@ -314,11 +314,15 @@ resolve(const st_options* opt, Resolved* r)
 // storage != 0 (ST_STORE_F16 / ST_STORE_BF16, T = float): d_mat holds n x n
 // 16-bit elements and is read only - the matrix-free loop with the launchers
 // of st_half.hip for K0 and the round (solve_device_half checks the options)
+// csr != nullptr: the matrix is that CSR handle (d_mat is not dereferenced) -
+// the same matrix-free loop with st_csr.hip's K0 and two-launch round, x in
+// the first (here unused) slot of the deferred ring
 template <typename T>
 int64_t
 solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
              T* eigen_val, uint32_t* iter_cnt, const st_options* opt,
-             st_stats* stats, bool flush_matrix = true, int storage = 0)
+             st_stats* stats, bool flush_matrix = true, int storage = 0,
+             const CsrHandle* csr = nullptr)
 {
   static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value,
                 "fp32 / fp64 vectors");
@@ -352,7 +356,7 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
     if (ensure_trace(c, row_bytes * o.max_itr))
       return -1;
   }
-  const bool mfree = storage != 0 || (o.flags & ST_FLAG_MATRIX_FREE) != 0;
+  const bool mfree = storage != 0 || csr || (o.flags & ST_FLAG_MATRIX_FREE) != 0;
   // large matrices: the flat round (k_flat + k_parts)
   const bool flat = !mfree && round_flat_pays(n, n, sizeof(T));
   // the flat round stores the matrix every kDefer rounds (bit-identical
@@ -369,7 +373,7 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   }
   // K0 takes the flat form wherever the flat round pays (the matrix-free
   // loop's too)
-  const bool flat_k0 = storage == 0 && round_flat_pays(n, n, sizeof(T));
+  const bool flat_k0 = storage == 0 && !csr && round_flat_pays(n, n, sizeof(T));
   if (flat_k0 && ensure_part(c, sizeof(T) * round_flat_scratch(n, n)))
     return -1;
   T* d_part = reinterpret_cast<T*>(c->d_part);
@@ -414,7 +418,10 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
     (void)hipEventRecord(ev[0], s);
   }
   T* const s0 = defer ? ring_s[0] : s_buf[0];
-  if (storage != 0) { // K0 on the 16-bit matrix
+  if (csr) { // K0 on the CSR matrix
+    if (launch_csr_rowsum(csr, s0, s))
+      return -1;
+  } else if (storage != 0) { // K0 on the 16-bit matrix
     if constexpr (std::is_same<T, float>::value) {
       if (launch_rowsum_half(storage, d_mat, s0, n, n, s))
         return -1;
@@ -452,7 +459,11 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
         ev.push_back(eb);
         (void)hipEventRecord(ea, s);
       }
-      if (storage != 0) { // launch k+1 evaluates round k
+      if (csr) // launch k+1 evaluates round k
+        rc |= launch_csr_round(csr, s_buf[cur], s_buf[cur ^ 1], vb[k & 1],
+                               vb[(k + 1) & 1], ring_s[0], o.eps, k + 1,
+                               o.max_itr, o.semantics, c->d_state, s);
+      else if (storage != 0) { // launch k+1 evaluates round k
         if constexpr (std::is_same<T, float>::value)
           rc |= launch_mfree_half(storage, d_mat, s_buf[cur], s_buf[cur ^ 1],
                                   vb[k & 1], vb[(k + 1) & 1], n, n, 0, eps,
@@ -629,6 +640,88 @@ solve_host_half(Context* c, int storage, const void* mat, uint32_t n,
   st_stats local{};
   if (solve_device_half(c, storage, c->d_mat, n, nullptr, eigen_vec, eigen_val,
                         iter_cnt, opt, &local) < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
+}
+
+// The solve on a validated CSR matrix (st_csr_create): solve_device's
+// matrix-free loop with the CSR launchers.  Everything is checked before
+// anything is enqueued.
+int64_t
+solve_csr(Context* c, const CsrHandle* h, void* d_v_out, void* v_host,
+          void* eigen_val, uint32_t* iter_cnt, const st_options* opt,
+          st_stats* stats)
+{
+  if (csr_check_flags(opt))
+    return -1;
+  ST_REQUIRE(c, "null queue");
+  ST_REQUIRE(c->device == h->device,
+             "csr solve: the matrix lives on device %d, the queue on %d",
+             h->device, c->device);
+  // never dereferenced: solve_device reads the matrix through the handle
+  void* tag = const_cast<CsrHandle*>(h);
+  if (h->dtype)
+    return solve_device<double>(c, static_cast<double*>(tag), h->n,
+                                static_cast<double*>(d_v_out),
+                                static_cast<double*>(v_host),
+                                static_cast<double*>(eigen_val), iter_cnt, opt,
+                                stats, false, 0, h);
+  return solve_device<float>(c, static_cast<float*>(tag), h->n,
+                             static_cast<float*>(d_v_out),
+                             static_cast<float*>(v_host),
+                             static_cast<float*>(eigen_val), iter_cnt, opt,
+                             stats, false, 0, h);
+}
+
+// the context's cached device workspace holds the three arrays of a host
+// matrix: [row_ptr | vals | col_idx], each at a 256-byte aligned offset
+int64_t
+solve_host_csr(Context* c, int dtype, uint32_t n, uint64_t nnz,
+               const int64_t* row_ptr, const int32_t* col_idx, const void* vals,
+               void* eigen_val, void* eigen_vec, uint32_t* iter_cnt,
+               const st_options* opt, st_stats* stats)
+{
+  // host validation first: dtype, flags, then the matrix (row_ptr, col_idx)
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  if (csr_check_flags(opt))
+    return -1;
+  if (csr_check_host(dtype, n, nnz, row_ptr, col_idx, vals))
+    return -1;
+  ST_REQUIRE(eigen_val && eigen_vec && iter_cnt, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  const size_t elem = dtype ? 8 : 4;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
+               b_col = up(4 * nnz);
+  if (ensure_matrix(c, b_ptr + b_val + b_col))
+    return -1;
+  char* base = static_cast<char*>(c->d_mat);
+  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
+  void* d_val = base + b_ptr;
+  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
+                          hipMemcpyHostToDevice, c->stream));
+  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  CsrHandle* h = nullptr;
+  if (csr_create(dtype, n, nnz, d_ptr, d_col, d_val, c->stream, &h))
+    return -1;
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  const int64_t rc =
+    solve_csr(c, h, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local);
+  (void)csr_destroy(h);
+  if (rc < 0)
     return -1;
   local.h2d_ms = h2d;
   if (stats)
@@ -1100,6 +1193,23 @@ solve_vbatched_host(Context* c, const T* mats, const uint32_t* dims,
   return (int64_t)(h2d + local.loop_ms);
 }
 
+int
+csr_create_on(Context* c, int dtype, uint32_t n, uint64_t nnz,
+              const int64_t* d_row_ptr, const int32_t* d_col_idx,
+              const void* d_vals, void** out)
+{
+  ST_REQUIRE(out, "st_csr_create: null output pointer");
+  *out = nullptr;
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  CsrHandle* h = nullptr;
+  if (csr_create(dtype, n, nnz, d_row_ptr, d_col_idx, d_vals, c->stream, &h))
+    return -1;
+  *out = h;
+  return 0;
+}
+
 Context*
 as_ctx(void* wq)
 {
@@ -1347,6 +1457,44 @@ max_eigen_value_half_ex(void* wq, int storage, const void* mat,
   st::DeviceGuard guard;
   return st::solve_host_half(st::as_ctx(wq), storage, mat, dim, eigen_val,
                              eigen_vec, iter_cnt, opt, stats);
+}
+
+int
+st_csr_create(void* wq, int dtype, uint32_t n, uint64_t nnz,
+              const int64_t* d_row_ptr, const int32_t* d_col_idx,
+              const void* d_vals, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::csr_create_on(st::as_ctx(wq), dtype, n, nnz, d_row_ptr, d_col_idx,
+                           d_vals, out);
+}
+
+int64_t
+st_solve_csr(void* wq, void* csr, void* d_eigen_vec, void* eigen_vec_host,
+             void* eigen_val, unsigned int* iter_cnt, const st_options* opt,
+             st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  const st::CsrHandle* h = st::as_csr(csr, "st_solve_csr");
+  if (!h)
+    return -1;
+  return st::solve_csr(st::as_ctx(wq), h, d_eigen_vec, eigen_vec_host,
+                       eigen_val, iter_cnt, opt, stats);
+}
+
+int64_t
+max_eigen_value_csr_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                       const int64_t* row_ptr, const int32_t* col_idx,
+                       const void* vals, void* eigen_val, void* eigen_vec,
+                       unsigned int* iter_cnt, const st_options* opt,
+                       st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_csr(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
+                            vals, eigen_val, eigen_vec, iter_cnt, opt, stats);
 }
 
 int64_t

@@ -245,6 +245,109 @@ def mfree_round_half(mat0, s_prev, s_next, v_prev, v_cur, state, row0: int = 0,
         _stream(mat0.device)), "mfree_round_half")
 
 
+class CsrMatrix:
+    """A nonnegative sparse matrix in CSR storage on the device, validated and
+    planned (``st_csr_create``): the torch tensors (int64 ``crow_indices``
+    [n + 1], int32 ``col_indices`` [nnz], float32 / float64 ``values`` [nnz])
+    and the library's handle over them.
+
+    Built from ``(crow_indices, col_indices, values, n)`` - device tensors;
+    index dtypes are converted as needed, nothing else is copied - or from a
+    ``torch.sparse_csr`` tensor (``CsrMatrix(sparse)``).  Raises
+    ``EigenValueError`` naming the first offending row or entry when the
+    check kernel rejects the arrays; no handle exists then.  ``solver`` is
+    the ``DeviceSolver`` whose queue runs the check (one is made and closed
+    when None)."""
+
+    def __init__(self, crow_indices, col_indices=None, values=None, n: Optional[int] = None,
+                 *, solver: Optional["DeviceSolver"] = None):
+        torch = _torch()
+        self.handle = ctypes.c_void_p()
+        self.L = _lib.load()
+        if col_indices is None:
+            sp = crow_indices
+            if sp.layout != torch.sparse_csr:
+                raise TypeError(f"a torch.sparse_csr tensor required, got layout {sp.layout}")
+            assert sp.dim() == 2 and sp.shape[0] == sp.shape[1], "must be square"
+            n = sp.shape[0]
+            crow_indices, col_indices, values = (sp.crow_indices(), sp.col_indices(),
+                                                 sp.values())
+        _check_cuda(crow_indices, col_indices, values)
+        self.dtype_code = 1 if _sfx(values) == "f64" else 0
+        self.n = int(crow_indices.numel() - 1 if n is None else n)
+        if crow_indices.numel() != self.n + 1:
+            raise ValueError(f"crow_indices has {crow_indices.numel()} elements, n + 1 = "
+                             f"{self.n + 1} required")
+        if col_indices.numel() != values.numel():
+            raise ValueError("col_indices and values differ in length")
+        self.crow = crow_indices.to(torch.int64).contiguous()
+        self.col = col_indices.to(torch.int32).contiguous()
+        self.values = values.contiguous()
+        self.nnz = int(values.numel())
+        self.device = values.device
+        own = solver is None
+        solver = solver or DeviceSolver(self.device)
+        try:
+            _lib.check(self.L.st_set_stream(solver.q, _stream(self.device)), "st_set_stream")
+            _lib.check(self.L.st_csr_create(solver.q, self.dtype_code, self.n, self.nnz,
+                                            _ptr(self.crow), _ptr(self.col), _ptr(self.values),
+                                            ctypes.byref(self.handle)), "st_csr_create")
+        finally:
+            if own:
+                solver.close()
+
+    @property
+    def dtype(self):
+        return self.values.dtype
+
+    def plan(self):
+        """``(order, class_first)`` of the handle (``st_csr_get_plan``)."""
+        import numpy as np
+        order = np.zeros(self.n, dtype=np.uint32)
+        first = np.zeros(_lib.ST_CSR_CLASSES + 1, dtype=np.uint32)
+        _lib.check(self.L.st_csr_get_plan(self.handle, order.ctypes.data, first.ctypes.data),
+                   "st_csr_get_plan")
+        return order, first
+
+    def close(self) -> None:
+        if self.handle is not None and self.handle.value:
+            self.L.st_csr_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csr_rowsum(csr: CsrMatrix, out=None):
+    """s[r] = the sum of row r's entries (``st_csr_rowsum``): launch 0 of the
+    CSR matrix-free scheme."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(csr.n, dtype=csr.dtype, device=csr.device)
+    _check_cuda(out)
+    assert out.dtype == csr.dtype and out.numel() >= csr.n
+    _lib.check(_lib.load().st_csr_rowsum(csr.handle, _ptr(out), _stream(csr.device)),
+               "csr_rowsum")
+    return out
+
+
+def csr_mfree_round(csr: CsrMatrix, s_prev, s_next, v_prev, v_cur, x, state, *,
+                    eps: float = 1e-3, k: int = 1, max_itr: int = _lib.ST_MAX_ITR,
+                    semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Matrix-free launch k >= 1 on a CSR matrix (``st_csr_mfree_round``):
+    mfree_round's contract in two launches; ``x`` is scratch of n elements.
+    v_cur and the state are bit for bit mfree_round's on the densified matrix."""
+    _check_cuda(s_prev, s_next, v_prev, v_cur, x, state)
+    assert all(t.dtype == csr.dtype and t.numel() >= csr.n and t.is_contiguous()
+               for t in (s_prev, s_next, v_prev, v_cur, x))
+    _lib.check(_lib.load().st_csr_mfree_round(
+        csr.handle, _ptr(s_prev), _ptr(s_next), _ptr(v_prev), _ptr(v_cur), _ptr(x), float(eps),
+        k, max_itr, semantics, _ptr(state), _stream(csr.device)), "csr_mfree_round")
+
+
 def flat_round_pays(nrows: int, ncols: int, dtype) -> bool:
     """Whether the flat round (st_round_flat) is the faster form for a block."""
     torch = _torch()
@@ -537,6 +640,37 @@ class DeviceSolver:
             self.q, storage, _ptr(work), n, _ptr(v), None, ctypes.byref(ev), ctypes.byref(it),
             ctypes.byref(opt), ctypes.byref(stats))
         _lib.check(rc, "st_solve_device_half")
+        return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def solve_csr(self, csr: "CsrMatrix", *, eps: Optional[float] = None, max_itr: int = 0,
+                  semantics: int = _lib.ST_SEM_SYCL, batch: int = 0, trace: bool = False,
+                  time_kernels: bool = False):
+        """The matrix-free solve of a sparse ``CsrMatrix`` (``st_solve_csr``):
+        nnz * (b + 4) bytes per round, read where the arrays lie.  Returns
+        (λ: float, v: tensor of the matrix's dtype, iterations: int, stats:
+        dict), as ``solve_half``.  ``last_round_sums()`` works after
+        ``trace``, ``last_round_times()`` after ``time_kernels``."""
+        torch = _torch()
+        if not isinstance(csr, CsrMatrix):
+            raise TypeError(f"a CsrMatrix required, got {type(csr).__name__} "
+                            "(solve takes dense tensors)")
+        if csr.device.index != (self.device.index if self.device.index is not None
+                                else torch.cuda.current_device()):
+            raise ValueError(f"matrix on {csr.device}, solver context on {self.device}")
+        v = torch.empty(csr.n, dtype=csr.dtype, device=csr.device)
+        ev = (ctypes.c_double if csr.dtype_code else ctypes.c_float)()
+        it = ctypes.c_uint32()
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace else 0))
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
+        stats = _lib.st_stats()
+        self._trace = (csr.n, csr.dtype)
+        _lib.check(self.L.st_set_stream(self.q, _stream(csr.device)), "st_set_stream")
+        rc = self.L.st_solve_csr(self.q, csr.handle, _ptr(v), None, ctypes.byref(ev),
+                                 ctypes.byref(it), ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(rc, "st_solve_csr")
         return float(ev.value), v, int(it.value), stats.as_dict()
 
     def last_round_times(self):

@@ -224,6 +224,66 @@ class EigenValue:
         _lib.check(ts, "max_eigen_value_half_ex", self.so_lib)
         return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
 
+    def similarity_transform_csr(self, indptr, indices=None, data=None, n: Optional[int] = None,
+                                 *, eps: Optional[float] = None, max_itr: int = 0,
+                                 semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
+                                 time_kernels: bool = False, trace_sums: bool = False):
+        """The matrix-free solve of a nonnegative SPARSE matrix in CSR storage
+        (``max_eigen_value_csr_ex``): ``indptr`` [n + 1], ``indices`` [nnz] and
+        ``data`` [nnz] (float32 or float64) as in ``scipy.sparse.csr_matrix``;
+        index arrays of any integer dtype are converted to int64 / int32.  A
+        ``scipy.sparse`` matrix or a ``torch.sparse_csr`` tensor passed as the
+        first argument is accepted too (converted to CSR on the host).  The
+        matrix is validated on the host - no empty row, every column inside
+        [0, n) - before anything is copied; the device reads nnz * (b + 4)
+        bytes per round.
+
+        Returns ``(λ, v, ts_ms, iterations)`` in the dtype of ``data``."""
+        if indices is None:
+            sp = indptr
+            if hasattr(sp, "crow_indices"):          # a torch.sparse_csr tensor
+                assert sp.dim() == 2 and sp.shape[0] == sp.shape[1], \
+                    "must be square matrix of floating points !"
+                n = sp.shape[0]
+                indptr, indices, data = (sp.crow_indices().cpu().numpy(),
+                                         sp.col_indices().cpu().numpy(),
+                                         sp.values().cpu().numpy())
+            elif hasattr(sp, "tocsr"):               # any scipy.sparse matrix / array
+                sp = sp.tocsr()
+                assert sp.shape[0] == sp.shape[1], "must be square matrix of floating points !"
+                n = sp.shape[0]
+                indptr, indices, data = sp.indptr, sp.indices, sp.data
+            else:
+                raise TypeError("indptr, indices, data arrays or a sparse matrix required, got "
+                                f"{type(sp).__name__}")
+        data = np.ascontiguousarray(data)
+        assert data.dtype.num in (11, 12), "dtype of data must be float32 or float64 !"
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.asarray(indices)
+        assert indices.dtype.kind in "iu", "indices must be an integer array !"
+        if indices.size and (indices.min() < -2**31 or indices.max() >= 2**31):
+            raise _lib.EigenValueError("csr: a column index does not fit int32")
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        n = len(indptr) - 1 if n is None else int(n)
+        assert len(indptr) == n + 1, "indptr must have n + 1 elements !"
+        assert len(indices) == len(data), "indices and data must have one length !"
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace_sums else 0))
+        self._trace = (n, data.dtype)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
+        eigen_val = np.empty(1, dtype=data.dtype)
+        eigen_vec = np.empty(n, dtype=data.dtype)
+        iter_cnt = np.zeros(1, dtype=np.uint32)
+        dtype = _lib.DTYPE_F32 if data.dtype == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_csr_ex(
+            self.sycl_q, dtype, n, len(data), indptr.ctypes.data, indices.ctypes.data,
+            data.ctypes.data, eigen_val.ctypes.data, eigen_vec.ctypes.data,
+            iter_cnt.ctypes.data, ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_csr_ex", self.so_lib)
+        return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
+
     def last_round_times(self) -> np.ndarray:
         """Per-round kernel times (ms) of the last ``similarity_transform_ex``
         call made with ``time_kernels=True`` (empty otherwise)."""

@@ -427,6 +427,96 @@ int st_allgather_f64(void* comm, const double* send, double* recv,
                      uint64_t count, void* stream);
 
 /* ---------------------------------------------------------------------- */
+/* 3c. sparse (CSR) solve                                                  */
+/* ---------------------------------------------------------------------- */
+
+/* The matrix-free solve on a nonnegative SPARSE matrix in CSR storage: the
+ * iteration, stop test, v, lambda, counts and semantics of
+ * st_solve_device_f32 / _f64 with ST_FLAG_MATRIX_FREE, with the sweep over a
+ * dense row replaced by a CSR row product - nnz * (b + 4) bytes per round.
+ * Storage: square n x n, 1 <= n < 2^31; row_ptr int64 [n + 1], col_idx int32
+ * [nnz], vals fp32 / fp64 [nnz] (dtype 0 / 1).  Column indices within a row
+ * need not be sorted; duplicates are legal and add up; no alignment beyond
+ * the element's own.  The sign of the values is not checked (as in the dense
+ * paths).
+ *
+ * Row classes: a row is shared by 4, 16, 64 (one wave) or 256 (one
+ * workgroup) lanes according to its OWN nnz (<= 16, <= 128, <= 2048, above);
+ * st_csr_class_limits returns the table.  The plan - built once per matrix -
+ * is the row indices sorted by class, row order kept within a class, and the
+ * class starts; a round's row products are ONE launch over all classes.
+ * Summation order of a row (fixed, no atomics): with L lanes, lane t takes
+ * the entries start + t, start + t + L, ... in storage order, one fused
+ * multiply-add each, then the L lanes combine by a fixed halving tree (L =
+ * 256: each wave's tree, then the 4 wave partials added in wave order).  A
+ * row's result depends only on its own entries and on x - not on the other
+ * rows of the matrix nor on where the row stands. */
+#define ST_CSR_CLASSES 4
+/* The class table for dtype (0 f32, 1 f64; the same for both today): the
+ * first min(cap, ST_CSR_CLASSES) entries of nnz_max (the largest nnz of a
+ * row of the class; 0xffffffff for the last) and lanes (either may be
+ * NULL).  Returns ST_CSR_CLASSES, or negative (bad dtype).  No GPU needed. */
+int st_csr_class_limits(int dtype, uint32_t* nnz_max, uint32_t* lanes, int cap);
+/* The plan of a HOST row_ptr [n + 1]: order_out[n] = the row indices sorted
+ * by class, row order kept within a class; class_first[ST_CSR_CLASSES + 1] =
+ * where each class starts in order_out.  Returns the number of non-empty
+ * classes, or negative: row_ptr[0] != 0, an empty row or a decreasing
+ * row_ptr (the message names the row), n outside [1, 2^31), null pointer.
+ * No GPU needed. */
+int st_csr_plan(const int64_t* row_ptr, uint32_t n, uint32_t* order_out,
+                uint32_t* class_first);
+/* The shape the CSR kernels were built with ("lanes=4,16,64,256
+ * nnz_max=16,128,2048,inf rows=8,4,2,1 unroll=1,2,4,8 prep_grid=2048": lanes
+ * per row and nnz limit of each class, rows the lanes of a row take side by
+ * side and entries of each in flight, the workgroup cap of the vector pass);
+ * tools record it next to their numbers.  On MI355X (tools/bench_csr.py,
+ * profiles/csr_solve.json, one interleaved run, n = 4194304): 0.633 / 1.981 /
+ * 7.702 ms per fp32 round at 8 / 32 / 128 random columns per row (715 / 635 /
+ * 582 GB/s: bound by the gathers of x), 0.639 ms (1968 GB/s) at 32 columns
+ * within 2048 of the diagonal; torch.mv on the same arrays took 13.5 - 19.9
+ * ms.  No GPU needed. */
+const char* st_csr_shape_desc(void);
+/* A matrix handle over DEVICE arrays, which are read only, not copied, and
+ * must stay alive and unchanged until st_csr_destroy.  Validation comes
+ * before any gather: first row_ptr on its own (row_ptr[0] == 0, strictly
+ * increasing - an empty row would divide by zero -, row_ptr[n] == nnz);
+ * only if that passes every col_idx[e], e in [0, nnz), against [0, n).
+ * The first offending row or entry is named in eigen_last_error() and no
+ * handle is made.  Then the plan is built on the device.  Runs on wq's
+ * stream and device and returns after it completed.  0 or negative. */
+int st_csr_create(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                  const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                  const void* d_vals, void** out);
+int st_csr_destroy(void* csr);
+/* The handle's plan (built on the device), copied to the host: order_out [n]
+ * and class_first [ST_CSR_CLASSES + 1], either may be NULL - what st_csr_plan
+ * gives for the same row_ptr.  Returns the number of non-empty classes, or
+ * negative. */
+int st_csr_get_plan(void* csr, uint32_t* order_out, uint32_t* class_first);
+/* The solve.  Output conventions of st_solve_device_*, in the handle's dtype
+ * (d_eigen_vec device [n] or NULL, then eigen_vec_host receives it;
+ * eigen_val one element; iter_cnt).  opt: eps < 0 selects the dtype's
+ * default; max_itr, semantics and batch as in st_solve_device_*;
+ * ST_FLAG_MATRIX_FREE is accepted and implied, ST_FLAG_TIME_KERNELS and
+ * ST_FLAG_TRACE_SUMS work; ST_FLAG_ROUND_LOOP, ST_FLAG_WRITE_EVERY_ROUND and
+ * ST_FLAG_BATCH_ROUNDS are errors ("not supported") - checked before
+ * anything is enqueued, never a fallback.  A reducible matrix (e.g. a row
+ * whose only entry is its diagonal) may never meet the stop test: the solve
+ * then ends at max_itr with converged = 0.  Returns loop ms or negative. */
+int64_t st_solve_csr(void* wq, void* csr, void* d_eigen_vec,
+                     void* eigen_vec_host, void* eigen_val,
+                     unsigned int* iter_cnt, const st_options* opt,
+                     st_stats* stats);
+/* The host-pointer twin: validates dtype, flags and the matrix ON THE HOST
+ * (same order and messages, before the queue is even looked at), copies the
+ * three arrays in, solves, copies out.  Returns h2d + loop ms or negative. */
+int64_t max_eigen_value_csr_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                               const int64_t* row_ptr, const int32_t* col_idx,
+                               const void* vals, void* eigen_val,
+                               void* eigen_vec, unsigned int* iter_cnt,
+                               const st_options* opt, st_stats* stats);
+
+/* ---------------------------------------------------------------------- */
 /* 4. step-level kernels (asynchronous on `stream`, a hipStream_t or NULL) */
 /* ---------------------------------------------------------------------- */
 
@@ -775,6 +865,26 @@ int st_narrow_f32(int storage, const float* d_in, void* d_out, uint64_t count,
  * GB/s, against 0.161 / 0.627 ms for st_mfree_round_f32 on the widened
  * matrix.  No GPU needed. */
 const char* st_half_shape_desc(void);
+
+/* The sparse (CSR) scheme, step by step (what st_solve_csr runs); `csr` is a
+ * st_csr_create handle, all vectors device [n] in the handle's dtype.
+ *   st_csr_rowsum       d_s[r] = the sum of row r's entries (launch 0: s_0)
+ *   st_csr_mfree_round  launch k >= 1, the contract of st_mfree_round_f32 /
+ *     _f64 in two launches: k_csr_prep writes x = v_prev * s_prev to d_x
+ *     (scratch of n elements, distinct from the four vectors) and folds max
+ *     and the stop test of s_prev through d_state's scratch words (left
+ *     zero), the last workgroup publishing round k-1; k_csr_spmv writes
+ *     s_next[r] = (sum of a * x[col]) / x[r] and v_cur[r] = v_prev[r] *
+ *     (s_prev[r] / m).  d_v_cur and every field of st_state are bit for bit
+ *     what st_mfree_round_* writes for the densified matrix and the same
+ *     arguments.  Both launches are no-ops once d_state->end says an earlier
+ *     round stopped.  eps is a double for both dtypes (rounded to float for
+ *     an fp32 handle). */
+int st_csr_rowsum(void* csr, void* d_s, void* stream);
+int st_csr_mfree_round(void* csr, const void* d_s_prev, void* d_s_next,
+                       const void* d_v_prev, void* d_v_cur, void* d_x,
+                       double eps, unsigned int k, unsigned int max_itr,
+                       unsigned int semantics, st_state* d_state, void* stream);
 
 /* Round epilogue on the full row-sum vector s[0..n): m = max(0, max s)
  * (find_max, similarity_transform.cpp:154-227), v[i] *= s[i]/m

@@ -14,12 +14,12 @@ if [ "${1:-run}" = build ]; then
   # the tuning build's ABI (-DST_TUNING_ABI=1): the driver checks the setters too
   FL="--offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -DST_TUNING_ABI=1 -I$ROOT/include -I$ROOT/eigen_value_amd/csrc"
   SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer"
-  for f in st_kernels st_solve st_multi st_rendezvous st_half; do
+  for f in st_kernels st_solve st_multi st_rendezvous st_half st_csr; do
     /opt/rocm/bin/hipcc $FL $SAN -c $ROOT/eigen_value_amd/csrc/$f.hip -o $D/$f.o &
   done
   wait
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $SAN -o $D/libsimilarity_transform.so \
-    $D/st_kernels.o $D/st_solve.o $D/st_multi.o $D/st_rendezvous.o $D/st_half.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+    $D/st_kernels.o $D/st_solve.o $D/st_multi.o $D/st_rendezvous.o $D/st_half.o $D/st_csr.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
   rm -f $D/*.o
   /opt/rocm/lib/llvm/bin/clang -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
     -I$ROOT/include $ROOT/tests/cpp/capi_sanitize.c -L$D -lsimilarity_transform \
