@@ -8,8 +8,9 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -Wall -Wextra -Wno-unused-parameter -Iinclude -Ieigen_value_amd/csrc
 SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hip \
             eigen_value_amd/csrc/st_multi.hip eigen_value_amd/csrc/st_rendezvous.hip \
-            eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip
-OBJ      := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
+            eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip \
+            eigen_value_amd/csrc/st_csr_batch.hip
+OBJ     := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
 # st_kernels compiled to also export the launch-table setters of
@@ -19,7 +20,8 @@ LIB_TUNING := eigen_value_amd/lib/libsimilarity_transform_tuning.so
 HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/csrc/st_internal.h \
             eigen_value_amd/csrc/st_device.h eigen_value_amd/csrc/st_rendezvous.h \
             eigen_value_amd/csrc/st_half.h eigen_value_amd/csrc/st_csr.h \
-            eigen_value_amd/csrc/st_csr_host.h
+            eigen_value_amd/csrc/st_csr_host.h eigen_value_amd/csrc/st_csr_batch.h \
+            eigen_value_amd/csrc/st_csr_plan.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 

@@ -327,6 +327,23 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_csr_rowsum.restype = i32
     L.st_csr_mfree_round.argtypes = [P, P, P, P, P, P, f64, u32, u32, u32, P, P]
     L.st_csr_mfree_round.restype = i32
+    L.st_csr_batch_create.argtypes = [P, i32, u32, P, u64, P, P, P,
+                                      ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_batch_create.restype = i32
+    L.st_csr_batch_destroy.argtypes = [P]
+    L.st_csr_batch_destroy.restype = i32
+    L.st_csr_batch_get_plan.argtypes = [P, P, P]
+    L.st_csr_batch_get_plan.restype = i32
+    L.st_csr_batch_shape_desc.argtypes = []
+    L.st_csr_batch_shape_desc.restype = ctypes.c_char_p
+    L.st_solve_csr_batched.argtypes = [P, P, P, P, P, P, P, P, P]
+    L.st_solve_csr_batched.restype = i64
+    L.max_eigen_value_csr_batched_ex.argtypes = [P, i32, u32, P, u64, P, P, P, P, P, P, P, P, P]
+    L.max_eigen_value_csr_batched_ex.restype = i64
+    L.st_csr_batch_rowsum.argtypes = [P, P, P]
+    L.st_csr_batch_rowsum.restype = i32
+    L.st_csr_batch_mfree_round.argtypes = [P, P, P, P, P, P, f64, u32, u32, u32, P, P, P]
+    L.st_csr_batch_mfree_round.restype = i32
 
 
 def batch_rounds_flag(round_loop, n: int, dtype_code: int) -> int:

@@ -84,13 +84,35 @@ csr_lanes_sum(T x)
 // end are redirected to entry 0 (always valid) and their products dropped, so
 // the sweep has no branch; a row's own order is untouched by R and U.
 // ONES: x ≡ 1, no division, no v (K0).
-template <typename T, int L, int R, int U, bool ONES>
+// G: what a row takes from outside itself.  CsrOne (one matrix): m and x as
+// passed, nothing else.  CsrStack (st_csr_batch.h: the stacked rows of a
+// batch): the row's own matrix b = row_mat[r] gives the gate (a row of a
+// matrix that ended before launch k is a row past `last`: live = false, no
+// entry read, nothing written - every lane still walks to the tree and the
+// barrier), m = states[b].max and the first row of the matrix's slice of x
+// (col is local to the matrix).  The lanes, the fma order and the tree are
+// the same for both.
+struct CsrOne
+{
+  static constexpr bool kStack = false;
+};
+struct CsrStack
+{
+  static constexpr bool kStack = true;
+  const uint32_t* row_mat;   // [N] the matrix of each stacked row
+  const uint32_t* mat_first; // [batch + 1] the first stacked row of each matrix
+  const st_state* states;    // [batch]
+  uint32_t k;                // this launch
+};
+
+template <typename T, int L, int R, int U, bool ONES, typename G = CsrOne>
 __device__ __forceinline__ void
 csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
          const T* __restrict__ vals, const uint32_t* __restrict__ order,
          uint32_t first, uint32_t last, uint32_t blk, const T* __restrict__ x,
          const T* __restrict__ s_prev, const T* __restrict__ v_prev,
-         T* __restrict__ s_next, T* __restrict__ v_cur, T m, T* red)
+         T* __restrict__ s_next, T* __restrict__ v_cur, T m, T* red,
+         const G g = G())
 {
   constexpr uint32_t RPB = kBlock / L; // rows side by side in a workgroup
   static_assert(L <= 64 || R == 1, "a workgroup-wide row stands alone");
@@ -103,6 +125,19 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const uint64_t i = (uint64_t)first + ((uint64_t)blk * R + j) * RPB + sub;
     live[j] = i < last;
     r[j] = live[j] ? order[i] : 0u;
+  }
+  T mr[R];         // CsrStack: the row's own m ...
+  uint32_t xo[R];  // ... and where its matrix starts in x
+  if constexpr (G::kStack) {
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      const uint32_t b = g.row_mat[r[j]];
+      const uint32_t en = __hip_atomic_load(&g.states[b].end, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+      live[j] = live[j] && !(en != 0 && en < g.k);
+      xo[j] = g.mat_first[b];
+      mr[j] = (T)g.states[b].max; // published by k_csrb_prep of this launch
+    }
   }
 #pragma unroll
   for (int j = 0; j < R; j++) {
@@ -142,6 +177,9 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
         a[j][u] = vals[at];
         if constexpr (ONES)
           xs[j][u] = (T)1;
+        else if constexpr (G::kStack) // a redirected load reads col[0], which is
+          // local to matrix 0: it gets no base, so x needs no slack past N
+          xs[j][u] = x[(in[j][u] ? (uint64_t)xo[j] : 0) + (uint32_t)col[at]];
         else
           xs[j][u] = x[col[at]];
       }
@@ -165,7 +203,10 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
           s_next[r[j]] = tot;
         } else {
           s_next[r[j]] = tot / xr[j];
-          v_cur[r[j]] = vp[j] * (sp[j] / m); // k_mfree's v update (cpp:260)
+          if constexpr (G::kStack)
+            v_cur[r[j]] = vp[j] * (sp[j] / mr[j]);
+          else
+            v_cur[r[j]] = vp[j] * (sp[j] / m); // k_mfree's v update (cpp:260)
         }
       }
     }
@@ -183,17 +224,21 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
         s_next[r[0]] = tot;
       } else {
         s_next[r[0]] = tot / xr[0];
-        v_cur[r[0]] = vp[0] * (sp[0] / m);
+        if constexpr (G::kStack)
+          v_cur[r[0]] = vp[0] * (sp[0] / mr[0]);
+        else
+          v_cur[r[0]] = vp[0] * (sp[0] / m);
       }
     }
   }
 }
 
-template <typename T, bool ONES>
+template <typename T, bool ONES, typename G = CsrOne>
 __device__ __forceinline__ void
 csr_dispatch(const int64_t* row_ptr, const int32_t* col, const T* vals,
              const uint32_t* order, const CsrTab& tab, const T* x,
-             const T* s_prev, const T* v_prev, T* s_next, T* v_cur, T m, T* red)
+             const T* s_prev, const T* v_prev, T* s_next, T* v_cur, T m, T* red,
+             const G g = G())
 {
   const uint32_t b = blockIdx.x;
   int c = 0; // workgroup-uniform
@@ -202,9 +247,9 @@ csr_dispatch(const int64_t* row_ptr, const int32_t* col, const T* vals,
   const uint32_t first = tab.row_first[c], last = tab.row_first[c + 1];
   const uint32_t blk = b - tab.blk_first[c];
 #define ST_CSR_ROWS(LL, CC)                                                        \
-  csr_rows<T, LL, csr::kRows[CC], csr::kUnroll[CC], ONES>(                     \
+  csr_rows<T, LL, csr::kRows[CC], csr::kUnroll[CC], ONES, G>(                  \
     row_ptr, col, vals, order, first, last, blk, x, s_prev, v_prev, s_next,    \
-    v_cur, m, red)
+    v_cur, m, red, g)
   static_assert(csr::kLanes[0] == 4 && csr::kLanes[1] == 16 &&
                   csr::kLanes[2] == 64 && csr::kLanes[3] == 256,
                 "the class bodies below");
@@ -291,142 +336,6 @@ k_csr_spmv(const int64_t* row_ptr, const int32_t* col, const T* vals,
   const T m = (T)state->max; // published by k_csr_prep of this launch k
   csr_dispatch<T, false>(row_ptr, col, vals, order, tab, x, s_prev, v_prev,
                          s_next, v_cur, m, red);
-}
-
-// ---------------------------------------------------------------------------
-// validation and plan, once per matrix (st_csr_create).  Nothing here reads
-// col_idx or vals except k_csr_check_col, which reads col_idx[0, nnz) only
-// and runs only after row_ptr passed.
-// ---------------------------------------------------------------------------
-// err[0] = the lowest offending row, err[1] = the lowest offending entry
-// (both start at ~0)
-__device__ __forceinline__ int
-csr_row_class(int64_t len)
-{
-  int c = 0;
-  while (c < csr::kClasses - 1 && (uint64_t)len > csr::kNnzMax[c])
-    c++;
-  return c;
-}
-
-// one row per lane: the row_ptr predicate of st_csr_host.h (row_bad), and
-// cnt[block][class] = the block's rows of each class
-__global__ __launch_bounds__(kBlock) void
-k_csr_check_ptr(const int64_t* __restrict__ row_ptr, uint32_t n, uint64_t nnz,
-                uint32_t* __restrict__ cnt, unsigned long long* err)
-{
-  const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  int cls = -1;
-  if (r < n) {
-    const int64_t a = row_ptr[r], b = row_ptr[r + 1];
-    const bool bad = (r == 0 && a != 0) || b <= a ||
-                     (r == (uint64_t)n - 1 && (uint64_t)b != nnz);
-    if (bad)
-      atomicMin(&err[0], (unsigned long long)r);
-    else
-      cls = csr_row_class(b - a);
-  }
-#pragma unroll
-  for (int c = 0; c < csr::kClasses; c++) {
-    const int k = __syncthreads_count(cls == c);
-    if (threadIdx.x == 0)
-      cnt[(uint64_t)blockIdx.x * csr::kClasses + c] = (uint32_t)k;
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void
-k_csr_check_col(const int32_t* __restrict__ col, uint32_t n, uint64_t nnz,
-                unsigned long long* err)
-{
-  for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < nnz;
-       e += (uint64_t)gridDim.x * kBlock) {
-    const int32_t c = col[e];
-    if (c < 0 || (uint32_t)c >= n)
-      atomicMin(&err[1], (unsigned long long)e);
-  }
-}
-
-// one workgroup: cnt[nblk][class] -> where the block's rows of that class
-// start in the plan (in place), and class_first[kClasses + 1]
-__global__ __launch_bounds__(kBlock) void
-k_csr_scan(uint32_t* __restrict__ cnt, uint32_t nblk,
-           uint32_t* __restrict__ class_first)
-{
-  __shared__ uint32_t part[kBlock][csr::kClasses];
-  __shared__ uint32_t cf[csr::kClasses + 1];
-  const uint32_t per = (nblk + kBlock - 1) / kBlock;
-  const uint64_t lo64 = (uint64_t)threadIdx.x * per;
-  const uint32_t lo = lo64 < nblk ? (uint32_t)lo64 : nblk;
-  const uint32_t hi = lo64 + per < nblk ? (uint32_t)(lo64 + per) : nblk;
-  uint32_t sum[csr::kClasses] = { 0, 0, 0, 0 };
-  for (uint32_t b = lo; b < hi; b++)
-#pragma unroll
-    for (int c = 0; c < csr::kClasses; c++)
-      sum[c] += cnt[(uint64_t)b * csr::kClasses + c];
-#pragma unroll
-  for (int c = 0; c < csr::kClasses; c++)
-    part[threadIdx.x][c] = sum[c];
-  __syncthreads();
-  if (threadIdx.x < csr::kClasses) { // exclusive scan over the 256 spans
-    uint32_t run = 0;
-    for (int t = 0; t < kBlock; t++) {
-      const uint32_t v = part[t][threadIdx.x];
-      part[t][threadIdx.x] = run;
-      run += v;
-    }
-    cf[threadIdx.x + 1] = run; // the class's total, for now
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    cf[0] = 0;
-    for (int c = 0; c < csr::kClasses; c++)
-      cf[c + 1] += cf[c];
-    for (int c = 0; c <= csr::kClasses; c++)
-      class_first[c] = cf[c];
-  }
-  __syncthreads();
-  uint32_t run[csr::kClasses];
-#pragma unroll
-  for (int c = 0; c < csr::kClasses; c++)
-    run[c] = cf[c] + part[threadIdx.x][c];
-  for (uint32_t b = lo; b < hi; b++)
-#pragma unroll
-    for (int c = 0; c < csr::kClasses; c++) {
-      const uint32_t v = cnt[(uint64_t)b * csr::kClasses + c];
-      cnt[(uint64_t)b * csr::kClasses + c] = run[c];
-      run[c] += v;
-    }
-}
-
-// order[base[block][class] + the row's rank among the block's rows of its
-// class] = row: stable within a class
-__global__ __launch_bounds__(kBlock) void
-k_csr_order(const int64_t* __restrict__ row_ptr, uint32_t n,
-            const uint32_t* __restrict__ base, uint32_t* __restrict__ order)
-{
-  __shared__ uint32_t wcnt[kBlock / 64][csr::kClasses];
-  const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int cls = -1;
-  if (r < n)
-    cls = csr_row_class(row_ptr[r + 1] - row_ptr[r]);
-  uint32_t rank = 0;
-#pragma unroll
-  for (int c = 0; c < csr::kClasses; c++) {
-    const unsigned long long mask = __ballot(cls == c);
-    if (cls == c)
-      rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0)
-      wcnt[wave][c] = (uint32_t)__popcll(mask);
-  }
-  __syncthreads();
-  if (cls >= 0) {
-    uint32_t at = base[(uint64_t)blockIdx.x * csr::kClasses + cls] + rank;
-    for (int w = 0; w < wave; w++)
-      at += wcnt[w][cls];
-    if (at < n) // always, for a row_ptr that did not change since the check
-      order[at] = (uint32_t)r;
-  }
 }
 
 } // namespace dev

@@ -4,6 +4,8 @@
 // st_csr_plan, st_csr_shape_desc, st_csr_destroy, st_csr_rowsum,
 // st_csr_mfree_round).  st_csr_create, st_solve_csr and
 // max_eigen_value_csr_ex live with the queue in st_solve.hip.
+// launch_csr_check_ptr and launch_csr_plan run the row_ptr check and the plan
+// kernels for st_csr_batch.hip, whose stacked rows take the same plan.
 
 #include <hip/hip_runtime.h>
 
@@ -12,6 +14,7 @@
 #include <new>
 
 #include "st_csr.h"
+#include "st_csr_plan.h"
 #include "st_internal.h"
 
 namespace st {
@@ -145,9 +148,7 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
 
   // 1. row_ptr on its own
   ST_CHECK(hipMemsetAsync(d_err, 0xff, 2 * sizeof(unsigned long long), stream));
-  hipLaunchKernelGGL(dev::k_csr_check_ptr, dim3(nblk), dim3(kBlock), 0, stream,
-                     d_row_ptr, n, nnz, d_cnt, d_err);
-  if (check_launch("csr_check_ptr"))
+  if (launch_csr_check_ptr(d_row_ptr, n, nnz, d_cnt, d_err, stream))
     return -1;
   ST_CHECK(hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, stream));
   ST_CHECK(hipStreamSynchronize(stream));
@@ -191,13 +192,7 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   // 3. the plan (order starts as zeros: every row index a kernel may read
   // from it is in range whatever happens)
   ST_CHECK(hipMemsetAsync(d_order, 0, sizeof(uint32_t) * (size_t)n, stream));
-  hipLaunchKernelGGL(dev::k_csr_scan, dim3(1), dim3(kBlock), 0, stream, d_cnt,
-                     nblk, d_cf);
-  if (check_launch("csr_scan"))
-    return -1;
-  hipLaunchKernelGGL(dev::k_csr_order, dim3(nblk), dim3(kBlock), 0, stream,
-                     d_row_ptr, n, (const uint32_t*)d_cnt, d_order);
-  if (check_launch("csr_order"))
+  if (launch_csr_plan(d_row_ptr, n, d_cnt, d_cf, d_order, stream))
     return -1;
   uint32_t cf[csr::kClasses + 1];
   ST_CHECK(hipMemcpyAsync(cf, d_cf, sizeof(cf), hipMemcpyDeviceToHost, stream));
@@ -230,6 +225,30 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   h->blk_first[csr::kClasses] = (uint32_t)blocks;
   *out = h;
   return 0;
+}
+
+int
+launch_csr_check_ptr(const int64_t* d_row_ptr, uint32_t n, uint64_t nnz,
+                     uint32_t* d_cnt, unsigned long long* d_err,
+                     hipStream_t stream)
+{
+  hipLaunchKernelGGL(dev::k_csr_check_ptr, dim3((n + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, stream, d_row_ptr, n, nnz, d_cnt, d_err);
+  return check_launch("csr_check_ptr");
+}
+
+int
+launch_csr_plan(const int64_t* d_row_ptr, uint32_t n, uint32_t* d_cnt,
+                uint32_t* d_cf, uint32_t* d_order, hipStream_t stream)
+{
+  const uint32_t nblk = (n + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(dev::k_csr_scan, dim3(1), dim3(kBlock), 0, stream, d_cnt,
+                     nblk, d_cf);
+  if (check_launch("csr_scan"))
+    return -1;
+  hipLaunchKernelGGL(dev::k_csr_order, dim3(nblk), dim3(kBlock), 0, stream,
+                     d_row_ptr, n, (const uint32_t*)d_cnt, d_order);
+  return check_launch("csr_order");
 }
 
 int

@@ -158,5 +158,144 @@ check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
   return check_col_idx(row_ptr, col_idx, n, nnz, msg, cap);
 }
 
+// ---------------------------------------------------------------------------
+// A batch in stacked CSR storage (st_csr_batch.hip): `batch` matrices, matrix
+// b of n_b = mat_first[b + 1] - mat_first[b] rows from stacked row
+// mat_first[b]; row_ptr [N + 1] over the concatenated entries; col_idx local
+// to its matrix.  The device check (st_csr_batch_create) applies the same
+// predicates and prints through the same describe_* functions.
+// ---------------------------------------------------------------------------
+// mat_first (always a host array): [0] == 0, strictly increasing (every
+// matrix has a row), N = mat_first[batch] < 2^31
+inline int
+check_mat_first(uint32_t batch, const uint32_t* mat_first, char* msg, size_t cap)
+{
+  if (batch == 0) {
+    snprintf(msg, cap, "csr batch: batch must be >= 1, got 0");
+    return -1;
+  }
+  if (!mat_first) {
+    snprintf(msg, cap, "csr batch: null mat_first");
+    return -1;
+  }
+  if (mat_first[0] != 0) {
+    snprintf(msg, cap, "csr batch: mat_first[0] must be 0, got %u", mat_first[0]);
+    return -1;
+  }
+  for (uint32_t b = 0; b < batch; b++)
+    if (mat_first[b + 1] <= mat_first[b]) {
+      snprintf(msg, cap,
+               "csr batch: mat_first does not increase at matrix %u "
+               "(mat_first[%u] = %u, mat_first[%u] = %u): every matrix has at "
+               "least one row", b, b, mat_first[b], b + 1, mat_first[b + 1]);
+      return -1;
+    }
+  if (mat_first[batch] >= 0x80000000u) {
+    snprintf(msg, cap,
+             "csr batch: N = mat_first[batch] must be below 2^31, got %u",
+             mat_first[batch]);
+    return -1;
+  }
+  return 0;
+}
+
+// the matrix b with mat_first[b] <= r < mat_first[b + 1] (r < N)
+inline uint32_t
+mat_of_row(const uint32_t* mat_first, uint32_t batch, uint32_t r)
+{
+  uint32_t lo = 0, hi = batch;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (mat_first[mid] <= r)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// the message for stacked row r (row_ptr[r] = a, row_ptr[r + 1] = b): the
+// matrix and its local row, then describe_row's text on the stacked arrays
+inline void
+describe_batch_row(const uint32_t* mat_first, uint32_t batch, uint32_t r,
+                   int64_t a, int64_t b, uint64_t nnz, char* msg, size_t cap)
+{
+  const uint32_t m = mat_of_row(mat_first, batch, r);
+  const int at = snprintf(msg, cap, "csr batch: matrix %u, local row %u: ", m,
+                          r - mat_first[m]);
+  if (at > 0 && (size_t)at < cap)
+    describe_row(r, a, b, mat_first[batch], nnz, msg + at, cap - (size_t)at);
+}
+
+// the message for entry e of stacked row r holding column c
+inline void
+describe_batch_col(const uint32_t* mat_first, uint32_t batch, uint32_t r,
+                   uint64_t e, int32_t c, char* msg, size_t cap)
+{
+  const uint32_t m = mat_of_row(mat_first, batch, r);
+  snprintf(msg, cap,
+           "csr batch: column index %d of entry %llu (matrix %u, local row %u) "
+           "is outside [0, %u): columns are local to their matrix", c,
+           (unsigned long long)e, m, r - mat_first[m],
+           mat_first[m + 1] - mat_first[m]);
+}
+
+// every column of matrix b inside [0, n_b) - which also proves that no entry
+// couples two matrices; call only after row_ptr passed
+inline int
+check_batch_col_idx(const uint32_t* mat_first, uint32_t batch,
+                    const int64_t* row_ptr, const int32_t* col_idx, char* msg,
+                    size_t cap)
+{
+  for (uint32_t m = 0; m < batch; m++) {
+    const uint32_t nb = mat_first[m + 1] - mat_first[m];
+    for (uint32_t r = mat_first[m]; r < mat_first[m + 1]; r++)
+      for (uint64_t e = (uint64_t)row_ptr[r]; e < (uint64_t)row_ptr[r + 1]; e++) {
+        const int32_t c = col_idx[e];
+        if (c < 0 || (uint32_t)c >= nb) {
+          describe_batch_col(mat_first, batch, r, e, c, msg, cap);
+          return -1;
+        }
+      }
+  }
+  return 0;
+}
+
+// a whole host batch, in the order the device check runs: dtype, mat_first,
+// the pointers, row_ptr over the N stacked rows, then the columns
+inline int
+check_batch_host(int dtype, uint32_t batch, const uint32_t* mat_first,
+                 uint64_t nnz, const int64_t* row_ptr, const int32_t* col_idx,
+                 const void* vals, char* msg, size_t cap)
+{
+  if (dtype != 0 && dtype != 1) {
+    snprintf(msg, cap, "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+    return -1;
+  }
+  if (check_mat_first(batch, mat_first, msg, cap))
+    return -1;
+  if (!row_ptr || !col_idx || !vals) {
+    snprintf(msg, cap, "csr: null row_ptr / col_idx / vals");
+    return -1;
+  }
+  const uint32_t n = mat_first[batch];
+  for (uint32_t r = 0; r < n; r++)
+    if (row_bad(r, row_ptr[r], row_ptr[r + 1], n, true, nnz)) {
+      describe_batch_row(mat_first, batch, r, row_ptr[r], row_ptr[r + 1], nnz,
+                         msg, cap);
+      return -1;
+    }
+  return check_batch_col_idx(mat_first, batch, row_ptr, col_idx, msg, cap);
+}
+
+// the participants (workgroups) of matrix b in the batch's vector pass
+// (k_csrb_prep): one per kBlock rows, at most prep_cap
+inline uint32_t
+batch_prep_wgs(uint32_t n_b, uint32_t prep_cap)
+{
+  const uint32_t want = (n_b + kBlock - 1) / kBlock;
+  return want < prep_cap ? want : prep_cap;
+}
+
 } // namespace csr
 } // namespace st

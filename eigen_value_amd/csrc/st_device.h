@@ -822,9 +822,9 @@ k_round_split(T* a, const T* __restrict__ s_cur, T* __restrict__ s_next,
 // thread 0 of each of `nwg` participating workgroups: fold the workgroup's
 // max (>= 0, not NaN) and failed-pair flag into st_state's scratch words;
 // the last of them to arrive publishes round k (exactly k_round's
-// bookkeeping) and clears the scratch
+// bookkeeping) and clears the scratch; true in that publishing thread only
 template <typename T>
-__device__ __forceinline__ void
+__device__ __forceinline__ bool
 stats_publish(T m, int fail, uint32_t nwg, const T* __restrict__ s, uint32_t k,
               uint32_t max_itr, uint32_t semantics, st_state* state)
 {
@@ -839,7 +839,7 @@ stats_publish(T m, int fail, uint32_t nwg, const T* __restrict__ s, uint32_t k,
   const uint32_t done_before = __hip_atomic_fetch_add(
     &state->arrivals, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
   if (done_before != nwg - 1)
-    return;
+    return false;
   // last arriver publishes round k
   const uint64_t mb = __hip_atomic_load(&state->max_bits, __ATOMIC_ACQUIRE,
                                         __HIP_MEMORY_SCOPE_AGENT);
@@ -864,6 +864,7 @@ stats_publish(T m, int fail, uint32_t nwg, const T* __restrict__ s, uint32_t k,
   state->max_bits = 0; // scratch back to zero for the next round
   state->fail = 0u;
   state->arrivals = 0u;
+  return true;
 }
 
 template <typename T, int BLK = kBlock>

@@ -174,6 +174,69 @@ int launch_csr_round(const CsrHandle* h, const void* s_prev, void* s_next,
                      const void* v_prev, void* v_cur, void* x, double eps,
                      uint32_t k, uint32_t max_itr, uint32_t semantics,
                      st_state* st, hipStream_t stream);
+// the two device passes of csr_create that a stacked batch shares: row_ptr's
+// predicate over n rows (d_err[0] = the lowest offending row, d_cnt
+// [ceil(n / 256)][4] = the rows of each class per block) and, from d_cnt,
+// the plan (d_cf [5] class starts, d_order [n])
+int launch_csr_check_ptr(const int64_t* d_row_ptr, uint32_t n, uint64_t nnz,
+                         uint32_t* d_cnt, unsigned long long* d_err,
+                         hipStream_t stream);
+int launch_csr_plan(const int64_t* d_row_ptr, uint32_t n, uint32_t* d_cnt,
+                    uint32_t* d_cf, uint32_t* d_order, hipStream_t stream);
+// a batch of sparse matrices in stacked CSR storage (st_csr_batch.hip),
+// validated, with the plan over its N stacked rows.  The three arrays stay
+// the caller's; the rest is the handle's own.
+struct CsrBatchHandle
+{
+  uint32_t magic; // kCsrBatchMagic while alive
+  int dtype;      // 0 = f32, 1 = f64
+  int device;
+  uint32_t batch;
+  uint32_t n; // N, the stacked rows
+  uint64_t nnz;
+  const int64_t* row_ptr;
+  const int32_t* col_idx;
+  const void* vals;
+  uint32_t* d_order;     // [N] stacked row indices sorted by class
+  uint32_t* d_aux;       // one allocation: the three arrays below
+  uint32_t* d_mat_first; // [batch + 1]
+  uint32_t* d_wg_first;  // [batch + 1] k_csrb_prep's first workgroup per matrix
+  uint32_t* d_row_mat;   // [N] the matrix of each stacked row
+  uint32_t prep_grid;    // wg_first[batch]
+  uint32_t row_first[5]; // class starts in d_order
+  uint32_t blk_first[5]; // class starts in the launch's workgroup range
+  uint32_t* mat_first;   // host copy [batch + 1]
+};
+constexpr uint32_t kCsrBatchMagic = 0x43535242u;
+// what k_csrb_collect hands the host of each matrix's st_state
+struct CsrBatchResult
+{
+  double lambda;
+  uint32_t iters, stop, end, done;
+};
+static_assert(sizeof(CsrBatchResult) == 24, "result layout");
+int csr_batch_check_flags(const st_options* opt);
+int csr_batch_check_host(int dtype, uint32_t batch, const uint32_t* mat_first,
+                         uint64_t nnz, const int64_t* row_ptr,
+                         const int32_t* col_idx, const void* vals);
+// validates on the device (mat_first on the host, row_ptr, then col_idx
+// against each matrix's own size), builds row_mat and the plan; synchronises
+int csr_batch_create(int dtype, uint32_t batch, const uint32_t* mat_first,
+                     uint64_t nnz, const int64_t* d_row_ptr,
+                     const int32_t* d_col_idx, const void* d_vals,
+                     hipStream_t stream, CsrBatchHandle** out);
+int csr_batch_destroy(CsrBatchHandle* h);
+const CsrBatchHandle* as_csr_batch(const void* p, const char* what);
+int launch_csrb_rowsum(const CsrBatchHandle* h, void* s, hipStream_t stream);
+int launch_csrb_round(const CsrBatchHandle* h, const void* s_prev, void* s_next,
+                      const void* v_prev, void* v_cur, void* x, double eps,
+                      uint32_t k, uint32_t max_itr, uint32_t semantics,
+                      st_state* states, uint32_t* finished, hipStream_t stream);
+// out [N] <- each matrix's final v from v0 / v1 by the parity of its end;
+// res [batch] <- the states
+int launch_csrb_collect(const CsrBatchHandle* h, const void* v0, const void* v1,
+                        void* out, const st_state* states, CsrBatchResult* res,
+                        hipStream_t stream);
 template <typename T>
 int launch_epilogue(const T* s, T* v, uint32_t n, T eps, uint32_t max_itr,
                     uint32_t semantics, st_state* st, hipStream_t stream);

@@ -729,6 +729,184 @@ solve_host_csr(Context* c, int dtype, uint32_t n, uint64_t nnz,
   return (int64_t)(h2d + local.loop_ms);
 }
 
+// The solve of a validated batch in stacked CSR storage
+// (st_csr_batch_create): solve_batched_rounds' host loop - one memset of the
+// states and the finished counter, one fill of v, K0, then opt->batch rounds
+// per look at the mirrored counter - with st_csr_batch.hip's two launches per
+// round for the whole batch.  Every matrix keeps its own state and stops in
+// its own round; k_csrb_collect picks each eigenvector from the ping-pong
+// buffer its end's parity names.  Everything is checked before anything is
+// enqueued.  Workspace: [s0 | s1 | v0 | v1 | x | out] in the vector buffer.
+template <typename T>
+int64_t
+solve_csr_batched_t(Context* c, const CsrBatchHandle* h, T* d_v_out, T* v_host,
+                    T* eigen_vals, uint32_t* iter_cnts, uint32_t* converged,
+                    const Resolved& o, st_stats* stats)
+{
+  const uint32_t batch = h->batch;
+  const size_t v_bytes = sizeof(T) * (size_t)h->n;
+  if (ensure_device(c) || ensure_vectors(c, v_bytes) || ensure_bstate(c, batch) ||
+      ensure_bsum(c, 256) || ensure_part(c, sizeof(CsrBatchResult) * (size_t)batch))
+    return -1;
+  auto slot = [&](int i) {
+    return reinterpret_cast<T*>((char*)c->d_vec + (size_t)i * c->vec_bytes);
+  };
+  T* s_buf[2] = { slot(0), slot(1) };
+  T* vb[2] = { slot(2), slot(3) };
+  T* d_x = slot(4);
+  T* d_v = d_v_out ? d_v_out : slot(5);
+  CsrBatchResult* d_res = static_cast<CsrBatchResult*>(c->d_part);
+  hipStream_t s = c->stream;
+  const uint32_t per_check = o.batch ? o.batch : kDefaultBatch;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)batch, s));
+  ST_CHECK(hipMemsetAsync(c->d_bcount, 0, sizeof(uint32_t), s));
+  if (launch_fill<T>(vb[0], h->n, (T)1, s))
+    return -1;
+  if (launch_csrb_rowsum(h, s_buf[0], s)) // K0
+    return -1;
+  uint32_t enqueued = 0, cur = 0, batch_no = 0;
+  bool done = false;
+  while (!done && enqueued < o.max_itr) {
+    const uint32_t b = (o.max_itr - enqueued) < per_check ? (o.max_itr - enqueued)
+                                                          : per_check;
+    for (uint32_t j = 0; j < b; j++) {
+      const uint32_t k = enqueued + j; // launch k+1 evaluates round k
+      if (launch_csrb_round(h, s_buf[cur], s_buf[cur ^ 1], vb[k & 1],
+                            vb[(k + 1) & 1], d_x, o.eps, k + 1, o.max_itr,
+                            o.semantics, c->d_bstate, c->d_bcount, s))
+        return -1;
+      cur ^= 1;
+    }
+    enqueued += b;
+    const int sl = batch_no & 1;
+    if (launch_count_mirror(c->d_bcount, &c->h_bcount[sl], s))
+      return -1;
+    ST_CHECK(hipEventRecord(c->ev_flag[sl], s));
+    // wait for the previous batch's count while this batch runs
+    if (batch_no > 0) {
+      ST_CHECK(hipEventSynchronize(c->ev_flag[sl ^ 1]));
+      done = c->h_bcount[sl ^ 1] >= batch;
+    }
+    batch_no++;
+  }
+  if (launch_csrb_collect(h, vb[0], vb[1], d_v, c->d_bstate, d_res, s))
+    return -1;
+  ST_CHECK(hipStreamSynchronize(s));
+  std::vector<CsrBatchResult> res(batch);
+  ST_CHECK(hipMemcpy(res.data(), d_res, sizeof(CsrBatchResult) * (size_t)batch,
+                     hipMemcpyDeviceToHost));
+  const double loop_ms = ms_since(t0);
+
+  const auto t1 = std::chrono::steady_clock::now();
+  uint32_t rounds = 0, all = 1;
+  for (uint32_t b = 0; b < batch; b++) {
+    const CsrBatchResult& fin = res[b];
+    ST_REQUIRE(fin.done, "internal: matrix %u ended without done flag", b);
+    eigen_vals[b] = (T)fin.lambda;
+    iter_cnts[b] = fin.iters;
+    if (converged)
+      converged[b] = fin.stop;
+    rounds = fin.end > rounds ? fin.end : rounds;
+    all &= fin.stop;
+  }
+  if (v_host)
+    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
+  const double d2h_ms = ms_since(t1);
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->loop_ms = loop_ms;
+    stats->d2h_ms = d2h_ms;
+    stats->rounds = rounds;
+    stats->converged = all;
+    stats->fused_launches = enqueued;
+  }
+  return (int64_t)loop_ms;
+}
+
+int64_t
+solve_csr_batched(Context* c, const CsrBatchHandle* h, void* d_v_out,
+                  void* v_host, void* eigen_vals, uint32_t* iter_cnts,
+                  uint32_t* converged, const st_options* opt, st_stats* stats)
+{
+  if (csr_batch_check_flags(opt))
+    return -1;
+  ST_REQUIRE(c, "null queue");
+  ST_REQUIRE(c->device == h->device,
+             "csr batched solve: the batch lives on device %d, the queue on %d",
+             h->device, c->device);
+  ST_REQUIRE(eigen_vals && iter_cnts, "null output pointer");
+  ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
+  Resolved o;
+  if (h->dtype ? resolve<double>(opt, &o) : resolve<float>(opt, &o))
+    return -1;
+  if (h->dtype)
+    return solve_csr_batched_t<double>(
+      c, h, static_cast<double*>(d_v_out), static_cast<double*>(v_host),
+      static_cast<double*>(eigen_vals), iter_cnts, converged, o, stats);
+  return solve_csr_batched_t<float>(
+    c, h, static_cast<float*>(d_v_out), static_cast<float*>(v_host),
+    static_cast<float*>(eigen_vals), iter_cnts, converged, o, stats);
+}
+
+// the host twin: [row_ptr | vals | col_idx] of the stacked batch in the
+// context's cached device workspace, as solve_host_csr
+int64_t
+solve_host_csr_batched(Context* c, int dtype, uint32_t batch,
+                       const uint32_t* mat_first, uint64_t nnz,
+                       const int64_t* row_ptr, const int32_t* col_idx,
+                       const void* vals, void* eigen_vals, void* eigen_vecs,
+                       uint32_t* iter_cnts, uint32_t* converged,
+                       const st_options* opt, st_stats* stats)
+{
+  // host validation first: dtype, flags, then the batch (mat_first, row_ptr,
+  // col_idx)
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  if (csr_batch_check_flags(opt))
+    return -1;
+  if (csr_batch_check_host(dtype, batch, mat_first, nnz, row_ptr, col_idx, vals))
+    return -1;
+  ST_REQUIRE(eigen_vals && eigen_vecs && iter_cnts, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  const uint32_t n = mat_first[batch];
+  const size_t elem = dtype ? 8 : 4;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
+               b_col = up(4 * nnz);
+  if (ensure_matrix(c, b_ptr + b_val + b_col))
+    return -1;
+  char* base = static_cast<char*>(c->d_mat);
+  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
+  void* d_val = base + b_ptr;
+  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
+                          hipMemcpyHostToDevice, c->stream));
+  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  CsrBatchHandle* h = nullptr;
+  if (csr_batch_create(dtype, batch, mat_first, nnz, d_ptr, d_col, d_val,
+                       c->stream, &h))
+    return -1;
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  const int64_t rc = solve_csr_batched(c, h, nullptr, eigen_vecs, eigen_vals,
+                                       iter_cnts, converged, opt, &local);
+  (void)csr_batch_destroy(h);
+  if (rc < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
+}
+
 template <typename T>
 int64_t
 solve_host(Context* c, const T* mat, uint32_t n, T* eigen_val, T* eigen_vec,
@@ -1210,6 +1388,25 @@ csr_create_on(Context* c, int dtype, uint32_t n, uint64_t nnz,
   return 0;
 }
 
+int
+csr_batch_create_on(Context* c, int dtype, uint32_t batch,
+                    const uint32_t* mat_first, uint64_t nnz,
+                    const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                    const void* d_vals, void** out)
+{
+  ST_REQUIRE(out, "st_csr_batch_create: null output pointer");
+  *out = nullptr;
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  CsrBatchHandle* h = nullptr;
+  if (csr_batch_create(dtype, batch, mat_first, nnz, d_row_ptr, d_col_idx, d_vals,
+                       c->stream, &h))
+    return -1;
+  *out = h;
+  return 0;
+}
+
 Context*
 as_ctx(void* wq)
 {
@@ -1495,6 +1692,49 @@ max_eigen_value_csr_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
   st::DeviceGuard guard;
   return st::solve_host_csr(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
                             vals, eigen_val, eigen_vec, iter_cnt, opt, stats);
+}
+
+int
+st_csr_batch_create(void* wq, int dtype, uint32_t batch,
+                    const uint32_t* mat_first, uint64_t nnz,
+                    const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                    const void* d_vals, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::csr_batch_create_on(st::as_ctx(wq), dtype, batch, mat_first, nnz,
+                                 d_row_ptr, d_col_idx, d_vals, out);
+}
+
+int64_t
+st_solve_csr_batched(void* wq, void* hp, void* d_eigen_vecs,
+                     void* eigen_vecs_host, void* eigen_vals,
+                     unsigned int* iter_cnts, unsigned int* converged,
+                     const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  const st::CsrBatchHandle* h = st::as_csr_batch(hp, "st_solve_csr_batched");
+  if (!h)
+    return -1;
+  return st::solve_csr_batched(st::as_ctx(wq), h, d_eigen_vecs, eigen_vecs_host,
+                               eigen_vals, iter_cnts, converged, opt, stats);
+}
+
+int64_t
+max_eigen_value_csr_batched_ex(void* wq, int dtype, uint32_t batch,
+                               const uint32_t* mat_first, uint64_t nnz,
+                               const int64_t* row_ptr, const int32_t* col_idx,
+                               const void* vals, void* eigen_vals,
+                               void* eigen_vecs, unsigned int* iter_cnts,
+                               unsigned int* converged, const st_options* opt,
+                               st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_csr_batched(st::as_ctx(wq), dtype, batch, mat_first, nnz,
+                                    row_ptr, col_idx, vals, eigen_vals,
+                                    eigen_vecs, iter_cnts, converged, opt, stats);
 }
 
 int64_t

@@ -348,6 +348,156 @@ def csr_mfree_round(csr: CsrMatrix, s_prev, s_next, v_prev, v_cur, x, state, *,
         k, max_itr, semantics, _ptr(state), _stream(csr.device)), "csr_mfree_round")
 
 
+class CsrBatch:
+    """Many nonnegative sparse matrices in STACKED CSR storage on the device,
+    validated and planned (``st_csr_batch_create``): ``crow_indices`` int64
+    [N + 1] over the concatenated entries, ``col_indices`` int32 [nnz] LOCAL
+    to their matrix, ``values`` float32 / float64 [nnz], and ``mat_first``
+    (host integers [B + 1]: the first stacked row of each matrix,
+    ``mat_first[B] == N``).  Index dtypes are converted as needed, nothing
+    else is copied.  ``CsrBatch.from_matrices`` builds one from single
+    matrices.  Raises ``EigenValueError`` naming the matrix and its local row
+    or entry when the check rejects the arrays; no handle exists then."""
+
+    def __init__(self, crow_indices, col_indices, values, mat_first, *,
+                 solver: Optional["DeviceSolver"] = None):
+        import numpy as np
+        torch = _torch()
+        self.handle = ctypes.c_void_p()
+        self.L = _lib.load()
+        _check_cuda(crow_indices, col_indices, values)
+        mf = np.asarray(mat_first)
+        if mf.ndim != 1 or mf.size < 2 or mf.dtype.kind not in "iu":
+            raise ValueError("mat_first must hold B + 1 >= 2 integers")
+        if (mf < 0).any() or (mf >= 2**32).any():
+            raise ValueError("mat_first does not fit uint32")
+        self.mat_first = np.ascontiguousarray(mf, dtype=np.uint32)
+        self.batch = int(mf.size - 1)
+        self.n = int(crow_indices.numel() - 1)
+        if int(self.mat_first[-1]) != self.n:
+            raise ValueError(f"mat_first[B] = {int(self.mat_first[-1])} must be N = "
+                             f"{self.n} (crow_indices has N + 1 elements)")
+        if col_indices.numel() != values.numel():
+            raise ValueError("col_indices and values differ in length")
+        self.dtype_code = 1 if _sfx(values) == "f64" else 0
+        self.crow = crow_indices.to(torch.int64).contiguous()
+        self.col = col_indices.to(torch.int32).contiguous()
+        self.values = values.contiguous()
+        self.nnz = int(values.numel())
+        self.device = values.device
+        own = solver is None
+        solver = solver or DeviceSolver(self.device)
+        try:
+            _lib.check(self.L.st_set_stream(solver.q, _stream(self.device)), "st_set_stream")
+            _lib.check(self.L.st_csr_batch_create(
+                solver.q, self.dtype_code, self.batch, self.mat_first.ctypes.data, self.nnz,
+                _ptr(self.crow), _ptr(self.col), _ptr(self.values),
+                ctypes.byref(self.handle)), "st_csr_batch_create")
+        finally:
+            if own:
+                solver.close()
+
+    @classmethod
+    def from_matrices(cls, mats, *, solver: Optional["DeviceSolver"] = None):
+        """From a sequence of ``(crow, col, values)`` triples of device tensors
+        or ``torch.sparse_csr`` tensors (square, one dtype, one device):
+        concatenated on the device, ``crow`` rebased, columns left as they
+        are."""
+        torch = _torch()
+        trip = []
+        for m in mats:
+            if isinstance(m, (tuple, list)):
+                if len(m) != 3:
+                    raise ValueError("a matrix is a (crow, col, values) triple")
+                trip.append(tuple(m))
+            elif getattr(m, "layout", None) == torch.sparse_csr:
+                assert m.dim() == 2 and m.shape[0] == m.shape[1], "must be square"
+                if m.crow_indices().numel() != m.shape[0] + 1:
+                    raise ValueError("crow_indices must have n + 1 elements")
+                trip.append((m.crow_indices(), m.col_indices(), m.values()))
+            else:
+                raise TypeError("(crow, col, values) triples or torch.sparse_csr tensors "
+                                f"required, got {type(m).__name__}")
+        if not trip:
+            raise ValueError("a CsrBatch needs at least one matrix")
+        dt = trip[0][2].dtype
+        for crow, col, vals in trip:
+            if vals.dtype != dt:
+                raise ValueError("all matrices must have one dtype")
+            if crow.numel() < 2:
+                raise ValueError("every matrix needs at least one row")
+            if col.numel() != vals.numel():
+                raise ValueError("col_indices and values differ in length")
+        mat_first = [0]
+        for crow, _, _ in trip:
+            mat_first.append(mat_first[-1] + int(crow.numel()) - 1)
+        parts = [torch.zeros(1, dtype=torch.int64, device=trip[0][0].device)]
+        base = parts[0][0]
+        for crow, _, _ in trip:                    # rebased on the device
+            c = crow.to(torch.int64)
+            parts.append(c[1:] - c[0] + base)
+            base = parts[-1][-1]
+        return cls(torch.cat(parts), torch.cat([t[1].to(torch.int32) for t in trip]),
+                   torch.cat([t[2] for t in trip]), mat_first, solver=solver)
+
+    @property
+    def dtype(self):
+        return self.values.dtype
+
+    def plan(self):
+        """``(order, class_first)`` over the N stacked rows
+        (``st_csr_batch_get_plan``): ``st_csr_plan`` of the stacked
+        ``crow_indices``."""
+        import numpy as np
+        order = np.zeros(self.n, dtype=np.uint32)
+        first = np.zeros(_lib.ST_CSR_CLASSES + 1, dtype=np.uint32)
+        _lib.check(self.L.st_csr_batch_get_plan(self.handle, order.ctypes.data,
+                                                first.ctypes.data), "st_csr_batch_get_plan")
+        return order, first
+
+    def close(self) -> None:
+        if self.handle is not None and self.handle.value:
+            self.L.st_csr_batch_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csr_batch_rowsum(batch: CsrBatch, out=None):
+    """s[r] = the sum of stacked row r's entries (``st_csr_batch_rowsum``):
+    launch 0 of the batched CSR scheme."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(batch.n, dtype=batch.dtype, device=batch.device)
+    _check_cuda(out)
+    assert out.dtype == batch.dtype and out.numel() >= batch.n
+    _lib.check(_lib.load().st_csr_batch_rowsum(batch.handle, _ptr(out), _stream(batch.device)),
+               "csr_batch_rowsum")
+    return out
+
+
+def csr_batch_mfree_round(batch: CsrBatch, s_prev, s_next, v_prev, v_cur, x, states, finished,
+                          *, eps: float = 1e-3, k: int = 1, max_itr: int = _lib.ST_MAX_ITR,
+                          semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Launch k >= 1 for a whole batch (``st_csr_batch_mfree_round``):
+    ``csr_mfree_round``'s contract for every matrix at once.  Vectors are
+    stacked [N]; ``states`` holds B states (64 bytes each, zero = fresh),
+    ``finished`` one uint32 / int32 word counting the matrices that ended."""
+    _check_cuda(s_prev, s_next, v_prev, v_cur, x, states, finished)
+    assert all(t.dtype == batch.dtype and t.numel() >= batch.n and t.is_contiguous()
+               for t in (s_prev, s_next, v_prev, v_cur, x))
+    assert states.is_contiguous() and states.numel() * states.element_size() >= 64 * batch.batch
+    assert finished.numel() * finished.element_size() >= 4
+    _lib.check(_lib.load().st_csr_batch_mfree_round(
+        batch.handle, _ptr(s_prev), _ptr(s_next), _ptr(v_prev), _ptr(v_cur), _ptr(x),
+        float(eps), k, max_itr, semantics, _ptr(states), _ptr(finished),
+        _stream(batch.device)), "csr_batch_mfree_round")
+
+
 def flat_round_pays(nrows: int, ncols: int, dtype) -> bool:
     """Whether the flat round (st_round_flat) is the faster form for a block."""
     torch = _torch()
@@ -672,6 +822,38 @@ class DeviceSolver:
                                  ctypes.byref(it), ctypes.byref(opt), ctypes.byref(stats))
         _lib.check(rc, "st_solve_csr")
         return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def solve_csr_batched(self, batch: "CsrBatch", *, eps: Optional[float] = None,
+                          max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
+                          batch_rounds: int = 0):
+        """The solve of a ``CsrBatch`` (``st_solve_csr_batched``): one pair of
+        launches per round for all matrices, each stopping in its own round
+        with the bits ``solve_csr`` gives it alone.  ``batch_rounds``: rounds
+        per host check (0 = 8).  Returns (λ: numpy [B], v: stacked tensor [N]
+        - matrix b's at ``batch.mat_first[b]`` -, iterations: uint32 numpy
+        [B], converged: uint32 numpy [B], stats: dict).  For ONE matrix
+        ``solve_csr`` is the call to use."""
+        import numpy as np
+        torch = _torch()
+        if not isinstance(batch, CsrBatch):
+            raise TypeError(f"a CsrBatch required, got {type(batch).__name__} "
+                            "(solve_csr takes a CsrMatrix)")
+        if batch.device.index != (self.device.index if self.device.index is not None
+                                  else torch.cuda.current_device()):
+            raise ValueError(f"batch on {batch.device}, solver context on {self.device}")
+        v = torch.empty(batch.n, dtype=batch.dtype, device=batch.device)
+        lam = np.empty(batch.batch, dtype=np.float64 if batch.dtype_code else np.float32)
+        its = np.zeros(batch.batch, dtype=np.uint32)
+        conv = np.zeros(batch.batch, dtype=np.uint32)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch_rounds, _lib.ST_FLAG_MATRIX_FREE)
+        stats = _lib.st_stats()
+        _lib.check(self.L.st_set_stream(self.q, _stream(batch.device)), "st_set_stream")
+        rc = self.L.st_solve_csr_batched(self.q, batch.handle, _ptr(v), None, lam.ctypes.data,
+                                         its.ctypes.data, conv.ctypes.data, ctypes.byref(opt),
+                                         ctypes.byref(stats))
+        _lib.check(rc, "st_solve_csr_batched")
+        return lam, v, its, conv, stats.as_dict()
 
     def last_round_times(self):
         """Per-round kernel times (ms) of the last solve made with

@@ -284,6 +284,83 @@ class EigenValue:
         _lib.check(ts, "max_eigen_value_csr_ex", self.so_lib)
         return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
 
+    @staticmethod
+    def _csr_triple(m):
+        """(indptr, indices, data, n) of one matrix of a sparse batch."""
+        if isinstance(m, (tuple, list)):
+            assert len(m) == 3, "a matrix is an (indptr, indices, data) triple !"
+            indptr, indices, data = (np.asarray(a) for a in m)
+            assert indptr.ndim == 1 and indices.ndim == 1 and data.ndim == 1, \
+                "indptr, indices and data must be one-dimensional !"
+            assert len(indptr) >= 2, "indptr must have n + 1 >= 2 elements !"
+            return indptr, indices, data, len(indptr) - 1
+        if hasattr(m, "crow_indices"):               # a torch.sparse_csr tensor
+            assert m.dim() == 2 and m.shape[0] == m.shape[1], \
+                "must be square matrices of floating points !"
+            return (m.crow_indices().cpu().numpy(), m.col_indices().cpu().numpy(),
+                    m.values().cpu().numpy(), int(m.shape[0]))
+        if hasattr(m, "tocsr"):                      # any scipy.sparse matrix / array
+            assert m.shape[0] == m.shape[1], "must be square matrices of floating points !"
+            m = m.tocsr()
+            return m.indptr, m.indices, m.data, int(m.shape[0])
+        raise TypeError("(indptr, indices, data) triples or sparse matrices required, got "
+                        f"{type(m).__name__}")
+
+    def similarity_transform_csr_batched(self, mats, *, eps: Optional[float] = None,
+                                         max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
+                                         batch_rounds: int = 0):
+        """MANY sparse matrices in one call (``max_eigen_value_csr_batched_ex``):
+        ``mats`` is a sequence of ``(indptr, indices, data)`` triples,
+        ``scipy.sparse`` matrices or ``torch.sparse_csr`` tensors, all square
+        and of one dtype (float32 or float64), sizes free; an empty sequence is
+        allowed.  They are concatenated into stacked CSR storage (``indptr``
+        rebased, columns stay local), validated on the host and solved with
+        one pair of launches per round for the whole batch; every matrix stops
+        in its own round and gets the bits ``similarity_transform_csr`` gives
+        it alone.  ``batch_rounds``: rounds per host check (0 = 8).
+
+        Returns ``(λ[B], [v_0 .. v_{B-1}], ts_ms, iterations[B])``, the shape
+        of ``similarity_transform_vbatched``'s result."""
+        trip = [self._csr_triple(m) for m in mats]
+        dt = np.asarray(trip[0][2]).dtype if trip else np.dtype(np.float32)
+        for indptr, indices, data, n in trip:
+            assert data.dtype == dt, "all matrices must have one dtype !"
+            assert len(indptr) == n + 1, "indptr must have n + 1 elements !"
+            assert n >= 1, "every matrix needs at least one row !"
+            assert len(indices) == len(data), "indices and data must have one length !"
+            assert np.asarray(indices).dtype.kind in "iu", "indices must be an integer array !"
+        assert dt.num in (11, 12), "dtype of data must be float32 or float64 !"
+        b = len(trip)
+        if b == 0:
+            return np.empty(0, dt), [], 0, np.zeros(0, np.uint32)
+        for _, indices, _, _ in trip:
+            if indices.size and (indices.min() < -2**31 or indices.max() >= 2**31):
+                raise _lib.EigenValueError("csr: a column index does not fit int32")
+        mat_first = np.concatenate([[0], np.cumsum([t[3] for t in trip])]).astype(np.int64)
+        assert mat_first[-1] < 2**31, "the batch must have fewer than 2^31 rows in all !"
+        mat_first = mat_first.astype(np.uint32)
+        ptrs, base = [np.zeros(1, np.int64)], 0
+        for indptr, _, _, _ in trip:               # rebase; validation is the library's
+            ip = np.asarray(indptr, dtype=np.int64)
+            ptrs.append(ip[1:] - ip[0] + base)
+            base = int(ptrs[-1][-1])
+        row_ptr = np.ascontiguousarray(np.concatenate(ptrs))
+        col = np.ascontiguousarray(np.concatenate([t[1] for t in trip]), dtype=np.int32)
+        vals = np.ascontiguousarray(np.concatenate([t[2] for t in trip]), dtype=dt)
+        eigen_vals = np.empty(b, dtype=dt)
+        eigen_vecs = np.empty(int(mat_first[-1]), dtype=dt)
+        iter_cnts = np.zeros(b, dtype=np.uint32)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch_rounds, _lib.ST_FLAG_MATRIX_FREE)
+        dtype = _lib.DTYPE_F32 if dt == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_csr_batched_ex(
+            self.sycl_q, dtype, b, mat_first.ctypes.data, len(vals), row_ptr.ctypes.data,
+            col.ctypes.data, vals.ctypes.data, eigen_vals.ctypes.data, eigen_vecs.ctypes.data,
+            iter_cnts.ctypes.data, None, ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_csr_batched_ex", self.so_lib)
+        vs = [eigen_vecs[int(mat_first[i]):int(mat_first[i + 1])] for i in range(b)]
+        return eigen_vals, vs, int(ts), iter_cnts
+
     def last_round_times(self) -> np.ndarray:
         """Per-round kernel times (ms) of the last ``similarity_transform_ex``
         call made with ``time_kernels=True`` (empty otherwise)."""

@@ -517,6 +517,81 @@ int64_t max_eigen_value_csr_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
                                const st_options* opt, st_stats* stats);
 
 /* ---------------------------------------------------------------------- */
+/* 3d. batched sparse (CSR) solve                                          */
+/* ---------------------------------------------------------------------- */
+
+/* Many sparse matrices in one call: every round is ONE pair of launches over
+ * the stacked rows of all matrices, every matrix keeps its own st_state and
+ * stops in its own round, and lambda, iterations, converged flag and
+ * eigenvector of each are bit for bit what st_solve_csr gives it alone with
+ * the same options (a row's product depends on its own entries and x only,
+ * its lane class on its own nnz, and max / stop test fold exactly under any
+ * partition).
+ *
+ * Stacked CSR: `batch` >= 1 matrices, matrix b square of n_b >= 1 rows,
+ * N = sum n_b < 2^31.
+ *   mat_first  HOST uint32 [batch + 1]: the first stacked row of each matrix;
+ *              mat_first[0] == 0, strictly increasing, mat_first[batch] == N
+ *              (N is read from here: a wrong last element shows as
+ *              row_ptr[N] != nnz)
+ *   row_ptr    int64 [N + 1] over the concatenated entries: row_ptr[0] == 0,
+ *              strictly increasing, row_ptr[N] == nnz
+ *   col_idx    int32 [nnz], LOCAL to its matrix: in [0, n_b)
+ *   vals       fp32 / fp64 [nnz] (dtype 0 / 1)
+ * i.e. the single-matrix arrays concatenated with row_ptr rebased.  Unsorted
+ * and duplicate columns stay legal.  Eigenvectors are stacked likewise:
+ * matrix b's at element mat_first[b].
+ *
+ * st_csr_batch_create: a handle over DEVICE arrays (read only, not copied,
+ * alive and unchanged until st_csr_batch_destroy); mat_first is copied.
+ * Validation before any gather: mat_first on the host, row_ptr's predicate
+ * over the N stacked rows, then every column against its OWN matrix's n_b (a
+ * column >= n_b but < N is refused: no entry couples two matrices).  The
+ * lowest offender is named in eigen_last_error() with its matrix and local
+ * row or entry, and no handle is made.  Then the plan over the N stacked
+ * rows - st_csr_plan of the stacked row_ptr - is built on the device.  A
+ * st_csr_create handle is refused by every call here, and a batch handle by
+ * every call of 3c. */
+int st_csr_batch_create(void* wq, int dtype, uint32_t batch,
+                        const uint32_t* mat_first, uint64_t nnz,
+                        const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                        const void* d_vals, void** out);
+int st_csr_batch_destroy(void* h);
+/* The handle's plan: order_out [N] and class_first [ST_CSR_CLASSES + 1],
+ * either may be NULL, as st_csr_get_plan. */
+int st_csr_batch_get_plan(void* h, uint32_t* order_out, uint32_t* class_first);
+/* The launch shape of the batch kernels, for tools to record
+ * (tools/bench_csr_batched.py; what it measured is in DESIGN.md, "Batched
+ * sparse solve").  No GPU needed. */
+const char* st_csr_batch_shape_desc(void);
+/* The solve.  d_eigen_vecs device [N] or NULL, then eigen_vecs_host receives
+ * the stacked eigenvectors; eigen_vals (the handle's dtype), iter_cnts and
+ * converged (may be NULL) are HOST arrays [batch].  opt: eps, max_itr,
+ * semantics and batch (rounds per host check, 0 = 8) as in st_solve_csr;
+ * ST_FLAG_MATRIX_FREE is accepted and implied; ST_FLAG_TIME_KERNELS,
+ * ST_FLAG_TRACE_SUMS, ST_FLAG_ROUND_LOOP, ST_FLAG_WRITE_EVERY_ROUND and
+ * ST_FLAG_BATCH_ROUNDS are errors ("not supported"), checked before anything
+ * is enqueued.  stats->rounds = the largest count of rounds any matrix
+ * evaluated, converged = 1 only if every matrix converged, fused_launches =
+ * the rounds enqueued.  For ONE matrix st_solve_csr is the call to use (see
+ * DESIGN.md, "Batched sparse solve").  Returns loop ms or negative. */
+int64_t st_solve_csr_batched(void* wq, void* h, void* d_eigen_vecs,
+                             void* eigen_vecs_host, void* eigen_vals,
+                             unsigned int* iter_cnts, unsigned int* converged,
+                             const st_options* opt, st_stats* stats);
+/* The host-pointer twin: validates dtype, flags, mat_first, row_ptr and the
+ * columns ON THE HOST (same predicates and messages, before the queue is
+ * even looked at), copies the arrays in, solves, copies out. */
+int64_t max_eigen_value_csr_batched_ex(void* wq, int dtype, uint32_t batch,
+                                       const uint32_t* mat_first, uint64_t nnz,
+                                       const int64_t* row_ptr,
+                                       const int32_t* col_idx, const void* vals,
+                                       void* eigen_vals, void* eigen_vecs,
+                                       unsigned int* iter_cnts,
+                                       unsigned int* converged,
+                                       const st_options* opt, st_stats* stats);
+
+/* ---------------------------------------------------------------------- */
 /* 4. step-level kernels (asynchronous on `stream`, a hipStream_t or NULL) */
 /* ---------------------------------------------------------------------- */
 
@@ -885,6 +960,28 @@ int st_csr_mfree_round(void* csr, const void* d_s_prev, void* d_s_next,
                        const void* d_v_prev, void* d_v_cur, void* d_x,
                        double eps, unsigned int k, unsigned int max_itr,
                        unsigned int semantics, st_state* d_state, void* stream);
+
+/* The batched sparse scheme, step by step (what st_solve_csr_batched runs);
+ * `h` is a st_csr_batch_create handle, all vectors device [N] stacked,
+ * d_states device [batch] (zero = fresh), d_finished one device word.
+ *   st_csr_batch_rowsum       K0 over the stacked rows
+ *   st_csr_batch_mfree_round  launch k >= 1 for the whole batch in two
+ *     launches.  k_csrb_prep: every workgroup works for exactly one matrix
+ *     (one per 256 of its rows, at most 2048), writes x = v_prev * s_prev for
+ *     its share and folds max and the stop test of the matrix's OWN s_prev
+ *     through d_states[b]; the last row's cyclic pair wraps to the matrix's
+ *     first row; the participant that publishes a round that sets `end` adds
+ *     1 to *d_finished.  k_csrb_spmv: st_csr_mfree_round's row products over
+ *     the batch's plan, gate and m from the row's own matrix's state, x
+ *     indexed from the matrix's first row.  Each matrix's slices of s_next,
+ *     v_cur and its state are bit for bit st_csr_mfree_round's on that
+ *     matrix alone; a matrix whose end is set and below k gets no writes. */
+int st_csr_batch_rowsum(void* h, void* d_s, void* stream);
+int st_csr_batch_mfree_round(void* h, const void* d_s_prev, void* d_s_next,
+                             const void* d_v_prev, void* d_v_cur, void* d_x,
+                             double eps, unsigned int k, unsigned int max_itr,
+                             unsigned int semantics, st_state* d_states,
+                             uint32_t* d_finished, void* stream);
 
 /* Round epilogue on the full row-sum vector s[0..n): m = max(0, max s)
  * (find_max, similarity_transform.cpp:154-227), v[i] *= s[i]/m
