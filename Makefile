@@ -9,7 +9,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hip \
             eigen_value_amd/csrc/st_multi.hip eigen_value_amd/csrc/st_rendezvous.hip \
             eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip \
-            eigen_value_amd/csrc/st_csr_batch.hip
+            eigen_value_amd/csrc/st_csr_batch.hip eigen_value_amd/csrc/st_csr_transpose.hip
 OBJ     := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
@@ -21,7 +21,7 @@ HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/c
             eigen_value_amd/csrc/st_device.h eigen_value_amd/csrc/st_rendezvous.h \
             eigen_value_amd/csrc/st_half.h eigen_value_amd/csrc/st_csr.h \
             eigen_value_amd/csrc/st_csr_host.h eigen_value_amd/csrc/st_csr_batch.h \
-            eigen_value_amd/csrc/st_csr_plan.h
+            eigen_value_amd/csrc/st_csr_plan.h eigen_value_amd/csrc/st_csr_transpose.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 

@@ -57,10 +57,10 @@ class st_stats(ctypes.Structure):
                 ("fused_launches", ctypes.c_uint32),
                 ("rounds", ctypes.c_uint32),
                 ("converged", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32)]
+                ("transpose_us", ctypes.c_uint32)]
 
     def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class st_launch_policy(ctypes.Structure):
@@ -323,6 +323,16 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_solve_csr.restype = i64
     L.max_eigen_value_csr_ex.argtypes = [P, i32, u32, u64, P, P, P, P, P, P, P, P]
     L.max_eigen_value_csr_ex.restype = i64
+    L.st_csr_transpose_host.argtypes = [i32, u32, u64, P, P, P, P, P, P]
+    L.st_csr_transpose_host.restype = i32
+    L.st_csr_transpose.argtypes = [P, P, P, P, P, ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_transpose.restype = i32
+    L.st_csr_transpose_scratch_bytes.argtypes = [u32, u64]
+    L.st_csr_transpose_scratch_bytes.restype = u64
+    L.st_csr_transpose_shape_desc.argtypes = []
+    L.st_csr_transpose_shape_desc.restype = ctypes.c_char_p
+    L.max_eigen_value_csr_left_ex.argtypes = [P, i32, u32, u64, P, P, P, P, P, P, P, P]
+    L.max_eigen_value_csr_left_ex.restype = i64
     L.st_csr_rowsum.argtypes = [P, P, P]
     L.st_csr_rowsum.restype = i32
     L.st_csr_mfree_round.argtypes = [P, P, P, P, P, P, f64, u32, u32, u32, P, P]
@@ -414,6 +424,44 @@ def csr_plan(row_ptr, L: Optional[ctypes.CDLL] = None):
     used = check(L.st_csr_plan(row_ptr.ctypes.data, max(n, 0), order.ctypes.data,
                                first.ctypes.data), "st_csr_plan", L)
     return order, first, used
+
+
+def csr_transpose_host(indptr, indices, data, L: Optional[ctypes.CDLL] = None):
+    """T(A) of a host CSR matrix (st_csr_transpose_host; no GPU): ``(t_indptr
+    int64 [n + 1], t_indices int32 [nnz], t_data [nnz])`` - the entries sorted
+    by column, entries of one column in storage order; numpy's ``p =
+    argsort(indices, kind="stable")``, ``rows[p]``, ``data[p]``.  ``data`` is
+    float32 or float64.  Raises EigenValueError for whatever the CSR solve
+    refuses, and naming the lowest column without an entry."""
+    import numpy as np
+    L = L or load()
+    data = np.ascontiguousarray(data)
+    if data.dtype not in (np.float32, np.float64):
+        raise TypeError(f"data must be float32 or float64, got {data.dtype}")
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    if len(indices) != len(data):
+        raise ValueError("indices and data differ in length")
+    n = len(indptr) - 1
+    t_ptr = np.zeros(max(n, 0) + 1, dtype=np.int64)
+    t_idx = np.zeros(len(data), dtype=np.int32)
+    t_val = np.zeros(len(data), dtype=data.dtype)
+    check(L.st_csr_transpose_host(DTYPE_F64 if data.dtype == np.float64 else DTYPE_F32,
+                                  max(n, 0), len(data), indptr.ctypes.data,
+                                  indices.ctypes.data, data.ctypes.data, t_ptr.ctypes.data,
+                                  t_idx.ctypes.data, t_val.ctypes.data),
+          "st_csr_transpose_host", L)
+    return t_ptr, t_idx, t_val
+
+
+def csr_transpose_shape(L: Optional[ctypes.CDLL] = None) -> dict:
+    """st_csr_transpose_shape_desc as a dict (integers where they are)."""
+    L = L or load()
+    out = {}
+    for item in L.st_csr_transpose_shape_desc().decode().split():
+        k, v = item.split("=")
+        out[k] = int(v) if v.isdigit() else v
+    return out
 
 
 def round_sums(L: ctypes.CDLL, q, n: int, dtype):

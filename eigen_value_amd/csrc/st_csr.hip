@@ -5,7 +5,8 @@
 // st_csr_mfree_round).  st_csr_create, st_solve_csr and
 // max_eigen_value_csr_ex live with the queue in st_solve.hip.
 // launch_csr_check_ptr and launch_csr_plan run the row_ptr check and the plan
-// kernels for st_csr_batch.hip, whose stacked rows take the same plan.
+// kernels for st_csr_batch.hip, whose stacked rows take the same plan, and
+// for st_csr_transpose.hip, which ends in csr_make_handle as csr_create does.
 
 #include <hip/hip_runtime.h>
 
@@ -197,6 +198,19 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   uint32_t cf[csr::kClasses + 1];
   ST_CHECK(hipMemcpyAsync(cf, d_cf, sizeof(cf), hipMemcpyDeviceToHost, stream));
   ST_CHECK(hipStreamSynchronize(stream));
+  CsrHandle* h = nullptr;
+  if (csr_make_handle(dtype, n, nnz, d_row_ptr, d_col_idx, d_vals, d_order, cf, &h))
+    return -1;
+  mem.p[2] = nullptr; // the handle's now
+  *out = h;
+  return 0;
+}
+
+int
+csr_make_handle(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
+                const int32_t* d_col_idx, const void* d_vals, uint32_t* d_order,
+                const uint32_t* cf, CsrHandle** out)
+{
   ST_REQUIRE(cf[0] == 0 && cf[csr::kClasses] == n,
              "internal: csr plan covers %u of %u rows", cf[csr::kClasses], n);
   for (int c = 0; c < csr::kClasses; c++)
@@ -213,7 +227,6 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   h->col_idx = d_col_idx;
   h->vals = d_vals;
   h->d_order = d_order;
-  mem.p[2] = nullptr; // the handle's now
   uint64_t blocks = 0;
   for (int c = 0; c < csr::kClasses; c++) {
     const uint32_t rpb = csr::kRows[c] * (kBlock / csr::kLanes[c]);

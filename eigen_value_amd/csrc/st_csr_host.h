@@ -159,6 +159,76 @@ check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
 }
 
 // ---------------------------------------------------------------------------
+// The transposition T(A) (st_csr_transpose.hip): t_row_ptr[c] = the entries
+// with column < c; transposed row c holds A's entries of column c in
+// ascending storage position (so ascending source row, duplicates of a row in
+// their order), t_col_idx their source rows, t_vals their values - a stable
+// sort of the entries by column.  The device path applies the same
+// predicates and prints through the same describe_* functions.
+// ---------------------------------------------------------------------------
+// the device sort carries 32-bit entry indices
+inline int
+check_transpose_nnz(uint64_t nnz, char* msg, size_t cap)
+{
+  if (nnz >= (1ull << 32)) {
+    snprintf(msg, cap,
+             "csr transpose: nnz must be below 2^32, got %llu: the sort "
+             "carries 32-bit entry indices", (unsigned long long)nnz);
+    return -1;
+  }
+  return 0;
+}
+
+inline void
+describe_empty_col(uint32_t c, char* msg, size_t cap)
+{
+  snprintf(msg, cap,
+           "csr transpose: column %u has no entry: row %u of the transposed "
+           "matrix would be empty and its row sum divided by zero", c, c);
+}
+
+// a counting sort; the outputs must not overlap the inputs
+inline int
+transpose_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
+               const int32_t* col_idx, const void* vals, int64_t* t_row_ptr,
+               int32_t* t_col_idx, void* t_vals, char* msg, size_t cap)
+{
+  if (check_transpose_nnz(nnz, msg, cap)) // before any array is read
+    return -1;
+  if (check_host(dtype, n, nnz, row_ptr, col_idx, vals, msg, cap))
+    return -1;
+  if (!t_row_ptr || !t_col_idx || !t_vals) {
+    snprintf(msg, cap, "csr transpose: null t_row_ptr / t_col_idx / t_vals");
+    return -1;
+  }
+  for (uint32_t c = 0; c <= n; c++)
+    t_row_ptr[c] = 0;
+  for (uint64_t e = 0; e < nnz; e++)
+    t_row_ptr[(uint32_t)col_idx[e] + 1]++;
+  for (uint32_t c = 0; c < n; c++) {
+    if (t_row_ptr[c + 1] == 0) { // the lowest one: nothing was added up yet
+      describe_empty_col(c, msg, cap);
+      return -1;
+    }
+    t_row_ptr[c + 1] += t_row_ptr[c];
+  }
+  // t_row_ptr[c] serves as column c's cursor and is put back afterwards
+  for (uint32_t r = 0; r < n; r++)
+    for (uint64_t e = (uint64_t)row_ptr[r]; e < (uint64_t)row_ptr[r + 1]; e++) {
+      const uint64_t at = (uint64_t)t_row_ptr[(uint32_t)col_idx[e]]++;
+      t_col_idx[at] = (int32_t)r;
+      if (dtype)
+        static_cast<double*>(t_vals)[at] = static_cast<const double*>(vals)[e];
+      else
+        static_cast<float*>(t_vals)[at] = static_cast<const float*>(vals)[e];
+    }
+  for (uint32_t c = n; c > 0; c--)
+    t_row_ptr[c] = t_row_ptr[c - 1];
+  t_row_ptr[0] = 0;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // A batch in stacked CSR storage (st_csr_batch.hip): `batch` matrices, matrix
 // b of n_b = mat_first[b + 1] - mat_first[b] rows from stacked row
 // mat_first[b]; row_ptr [N + 1] over the concatenated entries; col_idx local

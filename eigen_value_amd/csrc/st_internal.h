@@ -167,6 +167,19 @@ int csr_check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
 int csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
                const int32_t* d_col_idx, const void* d_vals, hipStream_t stream,
                CsrHandle** out);
+// the handle over checked arrays and their plan (d_order [n], which becomes
+// the handle's own; cf [5] the class starts on the host)
+int csr_make_handle(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
+                    const int32_t* d_col_idx, const void* d_vals,
+                    uint32_t* d_order, const uint32_t* cf, CsrHandle** out);
+// the stable transposition (st_csr_transpose.hip): T(a) into the caller's
+// device arrays, which must not overlap a's, and a handle over them with its
+// plan; synchronises `stream`.  The host twin needs no GPU.
+int csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
+                  void* d_t_vals, hipStream_t stream, CsrHandle** out);
+int csr_transpose_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
+                       const int32_t* col_idx, const void* vals,
+                       int64_t* t_row_ptr, int32_t* t_col_idx, void* t_vals);
 int csr_destroy(CsrHandle* h);
 const CsrHandle* as_csr(const void* p, const char* what); // null + error if not one
 int launch_csr_rowsum(const CsrHandle* h, void* s, hipStream_t stream);

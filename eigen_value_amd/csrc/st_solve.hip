@@ -729,6 +729,74 @@ solve_host_csr(Context* c, int dtype, uint32_t n, uint64_t nnz,
   return (int64_t)(h2d + local.loop_ms);
 }
 
+// The LEFT Perron vector of a host matrix: solve_host_csr on T(A), which is
+// made on the device.  The workspace holds A's three arrays, then T(A)'s:
+// [row_ptr | vals | col_idx | t_row_ptr | t_vals | t_col_idx].
+int64_t
+solve_host_csr_left(Context* c, int dtype, uint32_t n, uint64_t nnz,
+                    const int64_t* row_ptr, const int32_t* col_idx,
+                    const void* vals, void* eigen_val, void* eigen_vec,
+                    uint32_t* iter_cnt, const st_options* opt, st_stats* stats)
+{
+  ST_REQUIRE(nnz < (1ull << 32),
+             "csr transpose: nnz must be below 2^32, got %llu: the sort "
+             "carries 32-bit entry indices", (unsigned long long)nnz);
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  if (csr_check_flags(opt))
+    return -1;
+  if (csr_check_host(dtype, n, nnz, row_ptr, col_idx, vals))
+    return -1;
+  ST_REQUIRE(eigen_val && eigen_vec && iter_cnt, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  const size_t elem = dtype ? 8 : 4;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
+               b_col = up(4 * nnz), b_mat = b_ptr + b_val + b_col;
+  if (ensure_matrix(c, 2 * b_mat))
+    return -1;
+  char* base = static_cast<char*>(c->d_mat);
+  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
+  void* d_val = base + b_ptr;
+  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  int64_t* d_tptr = reinterpret_cast<int64_t*>(base + b_mat);
+  void* d_tval = base + b_mat + b_ptr;
+  int32_t* d_tcol = reinterpret_cast<int32_t*>(base + b_mat + b_ptr + b_val);
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
+                          hipMemcpyHostToDevice, c->stream));
+  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  CsrHandle* h = nullptr;
+  if (csr_create(dtype, n, nnz, d_ptr, d_col, d_val, c->stream, &h))
+    return -1;
+  const double h2d = ms_since(t0);
+  const auto t1 = std::chrono::steady_clock::now();
+  CsrHandle* ht = nullptr;
+  const int trc = csr_transpose(h, d_tptr, d_tcol, d_tval, c->stream, &ht);
+  (void)csr_destroy(h);
+  if (trc)
+    return -1;
+  const double tr_ms = ms_since(t1);
+  st_stats local{};
+  const int64_t rc =
+    solve_csr(c, ht, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local);
+  (void)csr_destroy(ht);
+  if (rc < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  const double us = tr_ms * 1000.0;
+  local.transpose_us = us < 4294967295.0 ? (uint32_t)us : 0xffffffffu;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + tr_ms + local.loop_ms);
+}
+
 // The solve of a validated batch in stacked CSR storage
 // (st_csr_batch_create): solve_batched_rounds' host loop - one memset of the
 // states and the finished counter, one fill of v, K0, then opt->batch rounds
@@ -1389,6 +1457,25 @@ csr_create_on(Context* c, int dtype, uint32_t n, uint64_t nnz,
 }
 
 int
+csr_transpose_on(Context* c, const CsrHandle* a, int64_t* d_t_row_ptr,
+                 int32_t* d_t_col_idx, void* d_t_vals, void** out)
+{
+  ST_REQUIRE(out, "st_csr_transpose: null output pointer");
+  *out = nullptr;
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  ST_REQUIRE(c->device == a->device,
+             "csr transpose: the matrix lives on device %d, the queue on %d",
+             a->device, c->device);
+  CsrHandle* h = nullptr;
+  if (csr_transpose(a, d_t_row_ptr, d_t_col_idx, d_t_vals, c->stream, &h))
+    return -1;
+  *out = h;
+  return 0;
+}
+
+int
 csr_batch_create_on(Context* c, int dtype, uint32_t batch,
                     const uint32_t* mat_first, uint64_t nnz,
                     const int64_t* d_row_ptr, const int32_t* d_col_idx,
@@ -1692,6 +1779,34 @@ max_eigen_value_csr_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
   st::DeviceGuard guard;
   return st::solve_host_csr(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
                             vals, eigen_val, eigen_vec, iter_cnt, opt, stats);
+}
+
+int
+st_csr_transpose(void* wq, void* csr, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
+                 void* d_t_vals, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (out)
+    *out = nullptr;
+  const st::CsrHandle* a = st::as_csr(csr, "st_csr_transpose");
+  if (!a)
+    return -1;
+  return st::csr_transpose_on(st::as_ctx(wq), a, d_t_row_ptr, d_t_col_idx,
+                              d_t_vals, out);
+}
+
+int64_t
+max_eigen_value_csr_left_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                            const int64_t* row_ptr, const int32_t* col_idx,
+                            const void* vals, void* eigen_val, void* eigen_vec,
+                            unsigned int* iter_cnt, const st_options* opt,
+                            st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_csr_left(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
+                                 vals, eigen_val, eigen_vec, iter_cnt, opt, stats);
 }
 
 int

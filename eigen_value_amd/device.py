@@ -257,7 +257,13 @@ class CsrMatrix:
     ``EigenValueError`` naming the first offending row or entry when the
     check kernel rejects the arrays; no handle exists then.  ``solver`` is
     the ``DeviceSolver`` whose queue runs the check (one is made and closed
-    when None)."""
+    when None).
+
+    ``transpose()`` gives T(A) as a new ``CsrMatrix`` (``st_csr_transpose``: a
+    stable sort of the entries by column on the device); ``.T`` is the same,
+    built once, kept, and closed with this matrix."""
+
+    _t = None
 
     def __init__(self, crow_indices, col_indices=None, values=None, n: Optional[int] = None,
                  *, solver: Optional["DeviceSolver"] = None):
@@ -309,7 +315,46 @@ class CsrMatrix:
                    "st_csr_get_plan")
         return order, first
 
+    def transpose(self, solver: Optional["DeviceSolver"] = None) -> "CsrMatrix":
+        """T(A) (``st_csr_transpose``): the entries sorted by column, those of
+        one column in storage order, in tensors torch allocates - bit for bit
+        ``csr_transpose_host`` of the same arrays.  Raises ``EigenValueError``
+        naming the lowest column without an entry (the transposed matrix
+        would have an empty row).  The result is independent of this matrix."""
+        torch = _torch()
+        if not self.handle.value:
+            raise ValueError("the matrix is closed")
+        t = object.__new__(CsrMatrix)
+        t.handle = ctypes.c_void_p()
+        t.L = self.L
+        t.dtype_code, t.n, t.nnz, t.device = self.dtype_code, self.n, self.nnz, self.device
+        t.crow = torch.empty(self.n + 1, dtype=torch.int64, device=self.device)
+        t.col = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
+        t.values = torch.empty(self.nnz, dtype=self.dtype, device=self.device)
+        own = solver is None
+        solver = solver or DeviceSolver(self.device)
+        try:
+            _lib.check(self.L.st_set_stream(solver.q, _stream(self.device)), "st_set_stream")
+            _lib.check(self.L.st_csr_transpose(solver.q, self.handle, _ptr(t.crow), _ptr(t.col),
+                                               _ptr(t.values), ctypes.byref(t.handle)),
+                       "st_csr_transpose")
+        finally:
+            if own:
+                solver.close()
+        return t
+
+    @property
+    def T(self) -> "CsrMatrix":
+        """``transpose()``, built at the first use and kept; closed with this
+        matrix."""
+        if self._t is None:
+            self._t = self.transpose()
+        return self._t
+
     def close(self) -> None:
+        if self._t is not None:
+            self._t.close()
+            self._t = None
         if self.handle is not None and self.handle.value:
             self.L.st_csr_destroy(self.handle)
             self.handle = ctypes.c_void_p()
@@ -319,6 +364,12 @@ class CsrMatrix:
             self.close()
         except Exception:
             pass
+
+
+def csr_transpose_host(indptr, indices, data):
+    """T(A) of host (numpy) CSR arrays by the library's host twin
+    (``st_csr_transpose_host``; no GPU): ``(t_indptr, t_indices, t_data)``."""
+    return _lib.csr_transpose_host(indptr, indices, data)
 
 
 def csr_rowsum(csr: CsrMatrix, out=None):
@@ -794,12 +845,19 @@ class DeviceSolver:
 
     def solve_csr(self, csr: "CsrMatrix", *, eps: Optional[float] = None, max_itr: int = 0,
                   semantics: int = _lib.ST_SEM_SYCL, batch: int = 0, trace: bool = False,
-                  time_kernels: bool = False):
+                  time_kernels: bool = False, left: bool = False):
         """The matrix-free solve of a sparse ``CsrMatrix`` (``st_solve_csr``):
         nnz * (b + 4) bytes per round, read where the arrays lie.  Returns
         (λ: float, v: tensor of the matrix's dtype, iterations: int, stats:
         dict), as ``solve_half``.  ``last_round_sums()`` works after
-        ``trace``, ``last_round_times()`` after ``time_kernels``."""
+        ``trace``, ``last_round_times()`` after ``time_kernels``.
+
+        ``left=True`` gives the LEFT Perron vector (v A = λ v; for a
+        row-stochastic P the stationary distribution is ``v / v.sum()``): the
+        solve of ``csr.T``, which is made on the device at the first use and
+        kept - bit for bit the solve of a host-transposed copy."""
+        if not isinstance(left, bool):
+            raise TypeError(f"left must be a bool, got {type(left).__name__}")
         torch = _torch()
         if not isinstance(csr, CsrMatrix):
             raise TypeError(f"a CsrMatrix required, got {type(csr).__name__} "
@@ -807,6 +865,11 @@ class DeviceSolver:
         if csr.device.index != (self.device.index if self.device.index is not None
                                 else torch.cuda.current_device()):
             raise ValueError(f"matrix on {csr.device}, solver context on {self.device}")
+        if left:
+            if csr._t is None:                     # csr.T, made on this solver's queue
+                csr._t = csr.transpose(self)
+            return self.solve_csr(csr.T, eps=eps, max_itr=max_itr, semantics=semantics,
+                                  batch=batch, trace=trace, time_kernels=time_kernels)
         v = torch.empty(csr.n, dtype=csr.dtype, device=csr.device)
         ev = (ctypes.c_double if csr.dtype_code else ctypes.c_float)()
         it = ctypes.c_uint32()

@@ -227,7 +227,8 @@ class EigenValue:
     def similarity_transform_csr(self, indptr, indices=None, data=None, n: Optional[int] = None,
                                  *, eps: Optional[float] = None, max_itr: int = 0,
                                  semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
-                                 time_kernels: bool = False, trace_sums: bool = False):
+                                 time_kernels: bool = False, trace_sums: bool = False,
+                                 left: bool = False):
         """The matrix-free solve of a nonnegative SPARSE matrix in CSR storage
         (``max_eigen_value_csr_ex``): ``indptr`` [n + 1], ``indices`` [nnz] and
         ``data`` [nnz] (float32 or float64) as in ``scipy.sparse.csr_matrix``;
@@ -238,7 +239,16 @@ class EigenValue:
         [0, n) - before anything is copied; the device reads nnz * (b + 4)
         bytes per round.
 
+        ``left=True`` gives the LEFT Perron vector, v A = λ v
+        (``max_eigen_value_csr_left_ex``): the matrix is transposed on the
+        device by a stable sort and the same solve runs on the result, bit for
+        bit the solve of a host-transposed copy.  A column without any entry
+        is refused by name.  For a row-stochastic matrix the stationary
+        distribution is ``v / v.sum()``.
+
         Returns ``(λ, v, ts_ms, iterations)`` in the dtype of ``data``."""
+        if not isinstance(left, bool):
+            raise TypeError(f"left must be a bool, got {type(left).__name__}")
         if indices is None:
             sp = indptr
             if hasattr(sp, "crow_indices"):          # a torch.sparse_csr tensor
@@ -277,11 +287,12 @@ class EigenValue:
         eigen_vec = np.empty(n, dtype=data.dtype)
         iter_cnt = np.zeros(1, dtype=np.uint32)
         dtype = _lib.DTYPE_F32 if data.dtype == np.float32 else _lib.DTYPE_F64
-        ts = self.so_lib.max_eigen_value_csr_ex(
+        name = "max_eigen_value_csr_left_ex" if left else "max_eigen_value_csr_ex"
+        ts = getattr(self.so_lib, name)(
             self.sycl_q, dtype, n, len(data), indptr.ctypes.data, indices.ctypes.data,
             data.ctypes.data, eigen_val.ctypes.data, eigen_vec.ctypes.data,
             iter_cnt.ctypes.data, ctypes.byref(opt), None)
-        _lib.check(ts, "max_eigen_value_csr_ex", self.so_lib)
+        _lib.check(ts, name, self.so_lib)
         return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
 
     @staticmethod

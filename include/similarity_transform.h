@@ -123,7 +123,8 @@ typedef struct st_stats
   uint32_t fused_launches;/* fused launches timed                         */
   uint32_t rounds;        /* row-sum evaluations performed                */
   uint32_t converged;     /* 1 if the stop test passed before max_itr     */
-  uint32_t reserved;
+  uint32_t transpose_us;  /* max_eigen_value_csr_left_ex: the device        */
+                          /* transposition, microseconds; 0 elsewhere      */
 } st_stats;
 
 /* Extended host-pointer solve.  dtype: 0 = float32, 1 = float64.
@@ -515,6 +516,70 @@ int64_t max_eigen_value_csr_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
                                const void* vals, void* eigen_val,
                                void* eigen_vec, unsigned int* iter_cnt,
                                const st_options* opt, st_stats* stats);
+
+/* Transposed CSR: the LEFT Perron vector (u A = lambda u; the stationary
+ * distribution of a row-stochastic P is u / sum(u)) is the right one of the
+ * transposed matrix.  T(A) is DEFINED as the stable sort of A's entries by
+ * column: t_row_ptr[c] = the number of entries with column < c; transposed
+ * row c holds A's entries of column c in ascending storage position (so in
+ * ascending source row, duplicates within a row in their order); t_col_idx
+ * is each entry's source row, t_vals its value - numpy's
+ * p = argsort(col_idx, kind="stable"), rows[p], vals[p].  The order in which a
+ * transposed row is summed is therefore a property of A alone, and every bit
+ * of a solve on the device's T(A) is that of a solve on a host-transposed
+ * copy.
+ *
+ * st_csr_transpose_host: the host twin, a counting sort.  Refuses nnz >= 2^32
+ * before any array is read (the device sort carries 32-bit entry indices),
+ * then everything max_eigen_value_csr_ex refuses with the same messages, then
+ * a column without any entry (the transposed matrix would have an empty row,
+ * which divides by zero; the message names the LOWEST such column).  The
+ * outputs ([n + 1] / [nnz] / [nnz]) must not overlap the inputs.  0 or
+ * negative.  No GPU needed. */
+int st_csr_transpose_host(int dtype, uint32_t n, uint64_t nnz,
+                          const int64_t* row_ptr, const int32_t* col_idx,
+                          const void* vals, int64_t* t_row_ptr,
+                          int32_t* t_col_idx, void* t_vals);
+/* The device transposition of a st_csr_create handle into the CALLER's device
+ * arrays d_t_row_ptr [n + 1], d_t_col_idx [nnz], d_t_vals [nnz] (aligned to
+ * their elements; refused when one overlaps an array of `csr` or another
+ * output - checked by address range), and *out = a handle over them with its
+ * plan built, of the same grade as st_csr_create's: a view, the arrays stay
+ * the caller's and must outlive it; destroyed with st_csr_destroy; accepted
+ * by every call of 3c and refused by those of 3d.  A hand-written stable LSD
+ * radix sort by column, digit_bits bits per pass, ceil(bits(n - 1) /
+ * digit_bits) passes of three launches (per-tile digit counts; a digit-major
+ * scan of the tile x digit table; the stable scatter, ranks from ballots of
+ * the digit's bits), then one gather of values and source rows through the
+ * permutation.  No float atomics, no workgroup waits on another, every
+ * computed destination is bounded.  t_row_ptr is the scan of the column
+ * histogram; the lowest empty column is reported before anything is
+ * scattered and no handle is made.  Runs on wq's stream and returns after it
+ * completed.  0 or negative. */
+int st_csr_transpose(void* wq, void* csr, int64_t* d_t_row_ptr,
+                     int32_t* d_t_col_idx, void* d_t_vals, void** out);
+/* Bytes of device scratch st_csr_transpose allocates and frees inside (the
+ * handle's plan, 4 n bytes, not counted); 0 for an n outside [1, 2^31) or
+ * nnz >= 2^32.  No GPU needed. */
+uint64_t st_csr_transpose_scratch_bytes(uint32_t n, uint64_t nnz);
+/* The shape the transposition was built with ("digit_bits=8 tile=2048
+ * rounds=8 lanes=256 col_block=2048 payload=index": bits per pass, entries
+ * per workgroup = rounds x lanes, columns per workgroup of the t_row_ptr
+ * scan, what travels with the key).  What tools/bench_csr_transpose.py
+ * measured with it is in DESIGN.md, "Transposed CSR".  No GPU needed. */
+const char* st_csr_transpose_shape_desc(void);
+/* max_eigen_value_csr_ex for the LEFT vector: validates on the host (nnz <
+ * 2^32, then as max_eigen_value_csr_ex), copies in, st_csr_transpose,
+ * st_solve_csr on the result, copies out.  stats->h2d_ms is the copy and A's
+ * check, stats->transpose_us the transposition, stats->loop_ms the solve.
+ * Returns h2d + transposition + loop ms or negative.  A function of its own
+ * and not a flag: the dense entry points ignore unknown flag bits. */
+int64_t max_eigen_value_csr_left_ex(void* wq, int dtype, uint32_t n,
+                                    uint64_t nnz, const int64_t* row_ptr,
+                                    const int32_t* col_idx, const void* vals,
+                                    void* eigen_val, void* eigen_vec,
+                                    unsigned int* iter_cnt,
+                                    const st_options* opt, st_stats* stats);
 
 /* ---------------------------------------------------------------------- */
 /* 3d. batched sparse (CSR) solve                                          */
