@@ -9,7 +9,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hip \
             eigen_value_amd/csrc/st_multi.hip eigen_value_amd/csrc/st_rendezvous.hip \
             eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip \
-            eigen_value_amd/csrc/st_csr_batch.hip eigen_value_amd/csrc/st_csr_transpose.hip
+            eigen_value_amd/csrc/st_csr_batch.hip eigen_value_amd/csrc/st_csr_transpose.hip \
+            eigen_value_amd/csrc/st_csr_terms.hip
 OBJ     := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
@@ -21,7 +22,8 @@ HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/c
             eigen_value_amd/csrc/st_device.h eigen_value_amd/csrc/st_rendezvous.h \
             eigen_value_amd/csrc/st_half.h eigen_value_amd/csrc/st_csr.h \
             eigen_value_amd/csrc/st_csr_host.h eigen_value_amd/csrc/st_csr_batch.h \
-            eigen_value_amd/csrc/st_csr_plan.h eigen_value_amd/csrc/st_csr_transpose.h
+            eigen_value_amd/csrc/st_csr_plan.h eigen_value_amd/csrc/st_csr_transpose.h \
+            eigen_value_amd/csrc/st_csr_terms.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 
@@ -56,8 +58,21 @@ probe: $(SRC) $(HDRS)
 oracle:
 	$(MAKE) -C oracle
 
+# the host side of the CSR solve with terms and empty rows (st_csr_host.h)
+# under the host sanitizers: a stand-alone program, run on the CPU, on the
+# table matrices of tests/csr_cases.py (needs the library for the class table)
+PYTHON ?= python
+csr_terms_sanitize: $(LIB) tests/cpp/csr_terms_sanitize.cpp eigen_value_amd/csrc/st_csr_host.h
+	@mkdir -p build/csr_tables
+	$(PYTHON) tests/csr_cases.py build/csr_tables
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	  -fno-omit-frame-pointer -Ieigen_value_amd/csrc tests/cpp/csr_terms_sanitize.cpp \
+	  -o build/csr_terms_sanitize
+	./build/csr_terms_sanitize build/csr_tables/table0.bin build/csr_tables/table1.bin \
+	  build/csr_tables/table2.bin
+
 clean:
 	rm -rf build eigen_value_amd/lib
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean probe
+.PHONY: all oracle clean probe csr_terms_sanitize

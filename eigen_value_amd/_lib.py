@@ -337,6 +337,33 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_csr_rowsum.restype = i32
     L.st_csr_mfree_round.argtypes = [P, P, P, P, P, P, f64, u32, u32, u32, P, P]
     L.st_csr_mfree_round.restype = i32
+    # low-rank terms and empty rows
+    L.st_csr_create_ex.argtypes = [P, i32, u32, u64, P, P, P, u32,
+                                   ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_create_ex.restype = i32
+    L.st_csr_empty_rows.argtypes = [P, P, P]
+    L.st_csr_empty_rows.restype = i32
+    L.st_csr_transpose_ex.argtypes = [P, P, P, P, P, u32, ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_transpose_ex.restype = i32
+    L.st_csr_transpose_host_ex.argtypes = [i32, u32, u64, P, P, P, P, P, P, u32]
+    L.st_csr_transpose_host_ex.restype = i32
+    L.st_csr_terms_create.argtypes = [P, P, u32, P, P, ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_terms_create.restype = i32
+    L.st_csr_terms_destroy.argtypes = [P]
+    L.st_csr_terms_destroy.restype = i32
+    L.st_csr_terms_scratch_bytes.argtypes = [u32, u32]
+    L.st_csr_terms_scratch_bytes.restype = u64
+    L.st_csr_terms_shape_desc.argtypes = []
+    L.st_csr_terms_shape_desc.restype = ctypes.c_char_p
+    L.st_solve_csr_terms.argtypes = [P, P, P, P, P, P, P, P, P]
+    L.st_solve_csr_terms.restype = i64
+    L.max_eigen_value_csr_terms_ex.argtypes = [P, i32, u32, u64, P, P, P, u32, P, P, u32,
+                                               P, P, P, P, P]
+    L.max_eigen_value_csr_terms_ex.restype = i64
+    L.st_csr_terms_rowsum.argtypes = [P, P, P, P, P]
+    L.st_csr_terms_rowsum.restype = i32
+    L.st_csr_terms_round.argtypes = [P, P, P, P, P, P, P, f64, u32, u32, u32, P, P]
+    L.st_csr_terms_round.restype = i32
     L.st_csr_batch_create.argtypes = [P, i32, u32, P, u64, P, P, P,
                                       ctypes.POINTER(ctypes.c_void_p)]
     L.st_csr_batch_create.restype = i32
@@ -392,6 +419,8 @@ def vbatched_plan(dims, dtype_code: int, L: Optional[ctypes.CDLL] = None):
 
 
 ST_CSR_CLASSES = 4
+ST_CSR_TERMS_MAX = 4
+ST_CSR_EMPTY_ROWS_OK = 1
 
 
 def csr_class_limits(dtype_code: int = DTYPE_F32, L: Optional[ctypes.CDLL] = None):
@@ -426,13 +455,16 @@ def csr_plan(row_ptr, L: Optional[ctypes.CDLL] = None):
     return order, first, used
 
 
-def csr_transpose_host(indptr, indices, data, L: Optional[ctypes.CDLL] = None):
+def csr_transpose_host(indptr, indices, data, L: Optional[ctypes.CDLL] = None,
+                       allow_empty: bool = False):
     """T(A) of a host CSR matrix (st_csr_transpose_host; no GPU): ``(t_indptr
     int64 [n + 1], t_indices int32 [nnz], t_data [nnz])`` - the entries sorted
     by column, entries of one column in storage order; numpy's ``p =
     argsort(indices, kind="stable")``, ``rows[p]``, ``data[p]``.  ``data`` is
     float32 or float64.  Raises EigenValueError for whatever the CSR solve
-    refuses, and naming the lowest column without an entry."""
+    refuses, and naming the lowest column without an entry.  ``allow_empty``
+    (st_csr_transpose_host_ex, ST_CSR_EMPTY_ROWS_OK): empty rows and empty
+    columns are legal."""
     import numpy as np
     L = L or load()
     data = np.ascontiguousarray(data)
@@ -446,12 +478,45 @@ def csr_transpose_host(indptr, indices, data, L: Optional[ctypes.CDLL] = None):
     t_ptr = np.zeros(max(n, 0) + 1, dtype=np.int64)
     t_idx = np.zeros(len(data), dtype=np.int32)
     t_val = np.zeros(len(data), dtype=data.dtype)
-    check(L.st_csr_transpose_host(DTYPE_F64 if data.dtype == np.float64 else DTYPE_F32,
-                                  max(n, 0), len(data), indptr.ctypes.data,
-                                  indices.ctypes.data, data.ctypes.data, t_ptr.ctypes.data,
-                                  t_idx.ctypes.data, t_val.ctypes.data),
-          "st_csr_transpose_host", L)
+    args = (DTYPE_F64 if data.dtype == np.float64 else DTYPE_F32, max(n, 0), len(data),
+            indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, t_ptr.ctypes.data,
+            t_idx.ctypes.data, t_val.ctypes.data)
+    if allow_empty:
+        check(L.st_csr_transpose_host_ex(*args, ST_CSR_EMPTY_ROWS_OK),
+              "st_csr_transpose_host_ex", L)
+    else:
+        check(L.st_csr_transpose_host(*args), "st_csr_transpose_host", L)
     return t_ptr, t_idx, t_val
+
+
+def csr_terms_shape(L: Optional[ctypes.CDLL] = None) -> dict:
+    """st_csr_terms_shape_desc as a dict (integers where they are)."""
+    L = L or load()
+    out = {}
+    for item in L.st_csr_terms_shape_desc().decode().split():
+        k, v = item.split("=")
+        out[k] = int(v) if v.isdigit() else v
+    return out
+
+
+def check_terms_arg(u, w, n: int):
+    """What every Python front checks of a terms argument before any library
+    call: ``u`` and ``w`` are [K, n] arrays or sequences of K vectors of n
+    elements, 1 <= K <= ST_CSR_TERMS_MAX, equally many of each.  Returns K."""
+    try:
+        ku, kw = len(u), len(w)
+    except TypeError:
+        raise TypeError("terms: u and w must be [K, n] arrays or sequences of K vectors")
+    if ku != kw:
+        raise ValueError(f"terms: {ku} vectors u but {kw} vectors w")
+    if not 1 <= ku <= ST_CSR_TERMS_MAX:
+        raise ValueError(f"terms: K must be in [1, {ST_CSR_TERMS_MAX}], got {ku}")
+    for name, vs in (("u", u), ("w", w)):
+        for j, x in enumerate(vs):
+            shape = tuple(getattr(x, "shape", (len(x),)))
+            if shape != (n,):
+                raise ValueError(f"terms: {name}_{j} has shape {shape}, ({n},) required")
+    return ku
 
 
 def csr_transpose_shape(L: Optional[ctypes.CDLL] = None) -> dict:

@@ -55,6 +55,23 @@ struct CsrTab
   uint32_t blk_first[csr::kClasses + 1];
 };
 
+// one element by a vector (per-lane) load, never through the scalar cache:
+// what an earlier launch of the same stream wrote (dots)
+__device__ __forceinline__ float
+ld_vector(const float* p)
+{
+  return __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t*>(p),
+                                           __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT));
+}
+__device__ __forceinline__ double
+ld_vector(const double* p)
+{
+  return __longlong_as_double((long long)__hip_atomic_load(
+    reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
+    __HIP_MEMORY_SCOPE_AGENT));
+}
+
 // the sum over the L lanes that share a row, valid in the row's last lane
 // (L <= 64) - wave_sum_l63's steps, cut off after log2(L)
 template <typename T, int L>
@@ -92,13 +109,37 @@ csr_lanes_sum(T x)
 // barrier), m = states[b].max and the first row of the matrix's slice of x
 // (col is local to the matrix).  The lanes, the fma order and the tree are
 // the same for both.
+// CsrTerms<T> (the operator A + sum_j u_j w_j^T, j < K <= 4): CsrOne, and
+// after the lane tree and before the division tot = fma(u_j[r], dots[j], tot),
+// j = 0 .. K-1 in that order; u_j[r] is asked for with the row's other
+// last-step loads, dots [K] (k_csr_dots of this launch) is read by a vector
+// load.  An empty row (legal under such an operator) takes no trip through
+// the sweep - e == end from the start - and its tot starts the fmas at 0.
+// KM >= K is the number of terms the instantiation holds registers for (the
+// u_j[r] live through the sweep: R * KM of them); it changes no result.
 struct CsrOne
 {
   static constexpr bool kStack = false;
+  static constexpr bool kTerms = false;
+  static constexpr int kK = 0;
+};
+constexpr int kCsrTermsMax = (int)csr::kTermsMax;
+template <typename T, int KM = kCsrTermsMax>
+struct CsrTerms
+{
+  static_assert(KM >= 1 && KM <= kCsrTermsMax, "1 .. ST_CSR_TERMS_MAX terms");
+  static constexpr bool kStack = false;
+  static constexpr bool kTerms = true;
+  static constexpr int kK = KM;
+  uint32_t K; // <= KM
+  const T* u[KM];
+  const T* dots;
 };
 struct CsrStack
 {
   static constexpr bool kStack = true;
+  static constexpr bool kTerms = false;
+  static constexpr int kK = 0;
   const uint32_t* row_mat;   // [N] the matrix of each stacked row
   const uint32_t* mat_first; // [batch + 1] the first stacked row of each matrix
   const st_state* states;    // [batch]
@@ -154,6 +195,14 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
       vp[j] = v_prev[r[j]];
     }
   }
+  T ut[R][G::kTerms ? G::kK : 1];
+  if constexpr (G::kTerms) {
+#pragma unroll
+    for (int j = 0; j < R; j++)
+#pragma unroll
+      for (int q = 0; q < G::kK; q++)
+        ut[j][q] = (uint32_t)q < g.K ? g.u[q][r[j]] : (T)0;
+  }
   T acc[R];
 #pragma unroll
   for (int j = 0; j < R; j++)
@@ -194,10 +243,21 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     }
   }
 
+  T dq[G::kTerms ? G::kK : 1];
+  if constexpr (G::kTerms) {
+#pragma unroll
+    for (int q = 0; q < G::kK; q++)
+      dq[q] = (uint32_t)q < g.K ? ld_vector(g.dots + q) : (T)0;
+  }
   if constexpr (L <= 64) {
 #pragma unroll
     for (int j = 0; j < R; j++) {
-      const T tot = csr_lanes_sum<T, L>(acc[j]);
+      T tot = csr_lanes_sum<T, L>(acc[j]);
+      if constexpr (G::kTerms) {
+#pragma unroll
+        for (int q = 0; q < G::kK; q++)
+          tot = (uint32_t)q < g.K ? __builtin_fma(ut[j][q], dq[q], tot) : tot;
+      }
       if (live[j] && t == L - 1) {
         if constexpr (ONES) {
           s_next[r[j]] = tot;
@@ -219,6 +279,11 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
 #pragma unroll
     for (int j = 1; j < kBlock / 64; j++)
       tot += red[j];
+    if constexpr (G::kTerms) {
+#pragma unroll
+      for (int q = 0; q < G::kK; q++)
+        tot = (uint32_t)q < g.K ? __builtin_fma(ut[0][q], dq[q], tot) : tot;
+    }
     if (live[0] && threadIdx.x == 0) {
       if constexpr (ONES) {
         s_next[r[0]] = tot;
@@ -264,6 +329,36 @@ csr_dispatch(const int64_t* row_ptr, const int32_t* col, const T* vals,
 #undef ST_CSR_ROWS
 }
 
+// The workgroup's share of up to four dots, from every lane's own sum:
+// wave_sum of each, the four wave sums added in wave order by lane 0, to
+// partial[q * gridDim.x + blockIdx.x].  Ends in a barrier, so the LDS it
+// uses is free again.
+template <typename T>
+__device__ __forceinline__ void
+csr_dot_partials(const T (&dacc)[kCsrTermsMax], uint32_t K, T* __restrict__ partial)
+{
+  __shared__ T dsh[kCsrTermsMax][kBlock / 64];
+#pragma unroll
+  for (int q = 0; q < kCsrTermsMax; q++)
+    if ((uint32_t)q < K) { // workgroup-uniform
+      const T w = wave_sum(dacc[q]);
+      if ((threadIdx.x & 63) == 0)
+        dsh[q][threadIdx.x >> 6] = w;
+    }
+  __syncthreads();
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int q = 0; q < kCsrTermsMax; q++)
+      if ((uint32_t)q < K) {
+        T tot = dsh[q][0];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; w++)
+          tot += dsh[q][w];
+        partial[(uint64_t)q * gridDim.x + blockIdx.x] = tot;
+      }
+  __syncthreads();
+}
+
 // K0: s[r] = Σ a (x ≡ 1)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void
@@ -275,13 +370,35 @@ k_csr_rowsum(const int64_t* row_ptr, const int32_t* col, const T* vals,
                         nullptr, s, nullptr, (T)0, red);
 }
 
-// launch k >= 1, first half: x, and round k-1's stats through the state
+// what the vector pass also does under CsrTerms: partial[j * gridDim.x +
+// blockIdx.x] = this workgroup's share of w_j . x (st_csr_terms.h has the
+// order)
 template <typename T>
+struct CsrDots
+{
+  uint32_t K;
+  const T* w[kCsrTermsMax];
+  T* partial; // [K][gridDim.x]
+};
+template <typename D>
+__device__ __forceinline__ const D&
+csr_first(const D& d)
+{
+  return d;
+}
+
+// launch k >= 1, first half: x, and round k-1's stats through the state.
+// DOTS is empty (k_csr_prep<T>, the kernel and the arguments it always had)
+// or one CsrDots<T> (k_csr_prep<T, CsrDots<T>>, the vector pass of a round
+// with terms): one body, in the kernel itself.
+template <typename T, typename... DOTS>
 __global__ __launch_bounds__(kBlock) void
 k_csr_prep(const T* __restrict__ s_prev, const T* __restrict__ v_prev,
            T* __restrict__ x, uint32_t n, T eps, uint32_t k, uint32_t max_itr,
-           uint32_t semantics, st_state* state)
+           uint32_t semantics, st_state* state, const DOTS... dots)
 {
+  constexpr bool kDots = sizeof...(DOTS) != 0;
+  static_assert(sizeof...(DOTS) <= 1, "at most one CsrDots");
   {
     const uint32_t e =
       __hip_atomic_load(&state->end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -292,15 +409,33 @@ k_csr_prep(const T* __restrict__ s_prev, const T* __restrict__ v_prev,
   const bool cyclic = semantics == ST_SEM_SYCL;
   T mx = (T)0; // find_max starts from 0 (cpp:185): negatives and NaN never win
   int fail = 0;
+  T dacc[kCsrTermsMax];
+  if constexpr (kDots) {
+#pragma unroll
+    for (int q = 0; q < kCsrTermsMax; q++)
+      dacc[q] = (T)0;
+  }
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n;
        i += (uint64_t)gridDim.x * kBlock) {
     const T sv = s_prev[i];
-    x[i] = v_prev[i] * sv;
+    const T xi = v_prev[i] * sv;
+    x[i] = xi;
+    if constexpr (kDots) {
+      const CsrDots<T>& d = csr_first(dots...);
+#pragma unroll
+      for (int q = 0; q < kCsrTermsMax; q++)
+        if ((uint32_t)q < d.K)
+          dacc[q] = __builtin_fma(d.w[q][i], xi, dacc[q]);
+    }
     mx = sv > mx ? sv : mx;
     if (i + 1 < n || cyclic) {
       const T d = sv - s_prev[i + 1 < n ? i + 1 : 0];
       fail |= (d < (T)0 ? -d : d) < eps ? 0 : 1; // cpp:419-421; NaN fails
     }
+  }
+  if constexpr (kDots) {
+    const CsrDots<T>& d = csr_first(dots...);
+    csr_dot_partials<T>(dacc, d.K, d.partial);
   }
   mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0)

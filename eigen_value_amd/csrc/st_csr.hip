@@ -99,10 +99,11 @@ csr_check_flags(const st_options* opt)
 
 int
 csr_check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
-               const int32_t* col_idx, const void* vals)
+               const int32_t* col_idx, const void* vals, uint32_t flags)
 {
   char msg[384];
-  if (csr::check_host(dtype, n, nnz, row_ptr, col_idx, vals, msg, sizeof(msg))) {
+  if (csr::check_host(dtype, n, nnz, row_ptr, col_idx, vals, msg, sizeof(msg),
+                      (flags & csr::kEmptyRowsOk) != 0)) {
     set_error("%s", msg);
     return -1;
   }
@@ -121,15 +122,36 @@ as_csr(const void* p, const char* what)
 }
 
 int
+csr_refuse_empty(const CsrHandle* h, const char* what)
+{
+  if (h->empty_rows == 0)
+    return 0;
+  char msg[384];
+  csr::describe_needs_terms(what, h->first_empty, h->empty_rows, msg, sizeof(msg));
+  set_error("%s", msg);
+  return -1;
+}
+
+int
 csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
            const int32_t* d_col_idx, const void* d_vals, hipStream_t stream,
-           CsrHandle** out)
+           CsrHandle** out, uint32_t flags)
 {
   ST_REQUIRE(out, "st_csr_create: null output pointer");
   *out = nullptr;
+  ST_REQUIRE((flags & ~csr::kEmptyRowsOk) == 0, "st_csr_create_ex: unknown flags %u",
+             flags);
+  const bool empty_ok = (flags & csr::kEmptyRowsOk) != 0;
   ST_REQUIRE(dtype == 0 || dtype == 1,
              "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
   ST_REQUIRE(n >= 1 && n < 0x80000000u, "csr: n must be in [1, 2^31), got %u", n);
+  if (empty_ok) { // arrays of no entry may be null
+    char m0[128];
+    if (csr::check_nnz_min(nnz, m0, sizeof(m0))) {
+      set_error("%s", m0);
+      return -1;
+    }
+  }
   ST_REQUIRE(d_row_ptr && d_col_idx && d_vals,
              "csr: null row_ptr / col_idx / vals");
   ST_REQUIRE(((uintptr_t)d_row_ptr & 7u) == 0 && ((uintptr_t)d_col_idx & 3u) == 0 &&
@@ -144,20 +166,30 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   uint32_t* d_cf = reinterpret_cast<uint32_t*>(d_err + 2);
   uint32_t* d_cnt = static_cast<uint32_t*>(mem.p[1]);
   uint32_t* d_order = static_cast<uint32_t*>(mem.p[2]);
+  uint32_t* d_empty = d_cf + 5; // the empty rows (ST_CSR_EMPTY_ROWS_OK)
   unsigned long long err[2];
   char msg[384];
 
   // 1. row_ptr on its own
   ST_CHECK(hipMemsetAsync(d_err, 0xff, 2 * sizeof(unsigned long long), stream));
-  if (launch_csr_check_ptr(d_row_ptr, n, nnz, d_cnt, d_err, stream))
+  ST_CHECK(hipMemsetAsync(d_empty, 0, sizeof(uint32_t), stream));
+  if (launch_csr_check_ptr(d_row_ptr, n, nnz, d_cnt, d_err, stream,
+                           empty_ok ? d_empty : nullptr))
     return -1;
   ST_CHECK(hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, stream));
   ST_CHECK(hipStreamSynchronize(stream));
+  const uint32_t first_empty = err[1] != ~0ull ? (uint32_t)err[1] : n;
+  uint32_t empty_rows = 0;
+  if (empty_ok && err[0] == ~0ull) {
+    ST_CHECK(hipMemcpy(&empty_rows, d_empty, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // err[1] serves the column check next
+    ST_CHECK(hipMemsetAsync(d_err + 1, 0xff, sizeof(unsigned long long), stream));
+  }
   if (err[0] != ~0ull) {
     const uint32_t r = (uint32_t)err[0];
     int64_t w[2];
     ST_CHECK(hipMemcpy(w, d_row_ptr + r, sizeof(w), hipMemcpyDeviceToHost));
-    csr::describe_row(r, w[0], w[1], n, nnz, msg, sizeof(msg));
+    csr::describe_row(r, w[0], w[1], n, nnz, msg, sizeof(msg), empty_ok);
     set_error("%s", msg);
     return -1;
   }
@@ -199,7 +231,8 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   ST_CHECK(hipMemcpyAsync(cf, d_cf, sizeof(cf), hipMemcpyDeviceToHost, stream));
   ST_CHECK(hipStreamSynchronize(stream));
   CsrHandle* h = nullptr;
-  if (csr_make_handle(dtype, n, nnz, d_row_ptr, d_col_idx, d_vals, d_order, cf, &h))
+  if (csr_make_handle(dtype, n, nnz, d_row_ptr, d_col_idx, d_vals, d_order, cf, &h,
+                      empty_rows, first_empty))
     return -1;
   mem.p[2] = nullptr; // the handle's now
   *out = h;
@@ -209,7 +242,8 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
 int
 csr_make_handle(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
                 const int32_t* d_col_idx, const void* d_vals, uint32_t* d_order,
-                const uint32_t* cf, CsrHandle** out)
+                const uint32_t* cf, CsrHandle** out, uint32_t empty_rows,
+                uint32_t first_empty)
 {
   ST_REQUIRE(cf[0] == 0 && cf[csr::kClasses] == n,
              "internal: csr plan covers %u of %u rows", cf[csr::kClasses], n);
@@ -227,6 +261,8 @@ csr_make_handle(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   h->col_idx = d_col_idx;
   h->vals = d_vals;
   h->d_order = d_order;
+  h->empty_rows = empty_rows;
+  h->first_empty = empty_rows ? first_empty : n;
   uint64_t blocks = 0;
   for (int c = 0; c < csr::kClasses; c++) {
     const uint32_t rpb = csr::kRows[c] * (kBlock / csr::kLanes[c]);
@@ -243,10 +279,11 @@ csr_make_handle(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
 int
 launch_csr_check_ptr(const int64_t* d_row_ptr, uint32_t n, uint64_t nnz,
                      uint32_t* d_cnt, unsigned long long* d_err,
-                     hipStream_t stream)
+                     hipStream_t stream, uint32_t* d_empty)
 {
   hipLaunchKernelGGL(dev::k_csr_check_ptr, dim3((n + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, stream, d_row_ptr, n, nnz, d_cnt, d_err);
+                     dim3(kBlock), 0, stream, d_row_ptr, n, nnz, d_cnt, d_err,
+                     d_empty);
   return check_launch("csr_check_ptr");
 }
 
@@ -421,7 +458,7 @@ st_csr_mfree_round(void* csr, const void* d_s_prev, void* d_s_next,
 {
   st::clear_error();
   const st::CsrHandle* h = st::as_csr(csr, "st_csr_mfree_round");
-  if (!h)
+  if (!h || st::csr_refuse_empty(h, "st_csr_mfree_round"))
     return -1;
   return st::launch_csr_round(h, d_s_prev, d_s_next, d_v_prev, d_v_cur, d_x, eps,
                               k, max_itr, semantics, d_state, ST_STREAM(stream));

@@ -1,8 +1,9 @@
 // st_csr_host.h — the host side of the sparse (CSR) solve that needs no GPU:
 // the row-class table, the plan (rows sorted by class) and the validation of
 // a host CSR matrix.  Plain C++ without any HIP, so that it also compiles
-// into a stand-alone program (tests/cpp/csr_sanitize.cpp, run under the host
-// sanitizers).  Included by st_csr.hip; not a public header.
+// into a stand-alone program (tests/cpp/csr_sanitize.cpp and, for the empty
+// rows flag and the low-rank terms, tests/cpp/csr_terms_sanitize.cpp, run
+// under the host sanitizers).  Included by st_csr.hip; not a public header.
 //
 // Every function returns 0 (or a count) on success and -1 on failure with
 // the reason written to msg[cap].
@@ -28,8 +29,13 @@ constexpr uint32_t kBlock = 256; // lanes of a workgroup
 // holds kRows[c] * 256 / kLanes[c] rows
 constexpr uint32_t kRows[kClasses] = { 8u, 4u, 2u, 1u };
 constexpr uint32_t kUnroll[kClasses] = { 1u, 2u, 4u, 8u };
+// flags of the _ex calls (ST_CSR_EMPTY_ROWS_OK) and the most rank-one terms
+// of one operator (ST_CSR_TERMS_MAX)
+constexpr uint32_t kEmptyRowsOk = 1u;
+constexpr uint32_t kTermsMax = 4;
 
-// the class of a row of `len` > 0 entries
+// the class of a row of `len` entries (an empty row, where a handle allows
+// one, is class 0)
 inline int
 row_class(uint64_t len)
 {
@@ -42,19 +48,20 @@ row_class(uint64_t len)
 // row_ptr on its own, row by row: row_ptr[0] == 0, strictly increasing (an
 // empty row would divide by zero), row_ptr[n] == nnz when check_nnz.  The
 // device check (k_csr_check_ptr) applies the same predicate per row and
-// reports the lowest offending row through describe_row.
+// reports the lowest offending row through describe_row.  empty_ok
+// (kEmptyRowsOk): b == a is legal, row_ptr only must not decrease.
 inline bool
 row_bad(uint32_t r, int64_t a, int64_t b, uint32_t n, bool check_nnz,
-        uint64_t nnz)
+        uint64_t nnz, bool empty_ok = false)
 {
-  return (r == 0 && a != 0) || b <= a ||
+  return (r == 0 && a != 0) || (empty_ok ? b < a : b <= a) ||
          (check_nnz && r == n - 1 && (uint64_t)b != nnz);
 }
 
 // the message for row r with row_ptr[r] = a, row_ptr[r + 1] = b
 inline void
 describe_row(uint32_t r, int64_t a, int64_t b, uint32_t n, uint64_t nnz,
-             char* msg, size_t cap)
+             char* msg, size_t cap, bool empty_ok = false)
 {
   if (r == 0 && a != 0)
     snprintf(msg, cap, "csr: row_ptr[0] must be 0, got %lld (row 0)",
@@ -63,7 +70,7 @@ describe_row(uint32_t r, int64_t a, int64_t b, uint32_t n, uint64_t nnz,
     snprintf(msg, cap,
              "csr: row_ptr decreases at row %u (row_ptr[%u] = %lld, "
              "row_ptr[%u] = %lld)", r, r, (long long)a, r + 1, (long long)b);
-  else if (b == a)
+  else if (b == a && !empty_ok)
     snprintf(msg, cap,
              "csr: row %u is empty (row_ptr[%u] = row_ptr[%u] = %lld): its "
              "row sum would be divided by zero", r, r, r + 1, (long long)a);
@@ -74,13 +81,54 @@ describe_row(uint32_t r, int64_t a, int64_t b, uint32_t n, uint64_t nnz,
 
 inline int
 check_row_ptr(const int64_t* row_ptr, uint32_t n, bool check_nnz, uint64_t nnz,
-              char* msg, size_t cap)
+              char* msg, size_t cap, bool empty_ok = false)
 {
   for (uint32_t r = 0; r < n; r++)
-    if (row_bad(r, row_ptr[r], row_ptr[r + 1], n, check_nnz, nnz)) {
-      describe_row(r, row_ptr[r], row_ptr[r + 1], n, nnz, msg, cap);
+    if (row_bad(r, row_ptr[r], row_ptr[r + 1], n, check_nnz, nnz, empty_ok)) {
+      describe_row(r, row_ptr[r], row_ptr[r + 1], n, nnz, msg, cap, empty_ok);
       return -1;
     }
+  return 0;
+}
+
+// the empty rows of a checked row_ptr: their number, *lowest = the first one
+// (n when there is none)
+inline uint32_t
+count_empty_rows(const int64_t* row_ptr, uint32_t n, uint32_t* lowest)
+{
+  uint32_t k = 0;
+  *lowest = n;
+  for (uint32_t r = 0; r < n; r++)
+    if (row_ptr[r + 1] == row_ptr[r]) {
+      if (k == 0)
+        *lowest = r;
+      k++;
+    }
+  return k;
+}
+
+// what a call that divides by a row sum of A alone says to an empty-rows
+// handle (st_solve_csr without terms, st_csr_mfree_round,
+// max_eigen_value_csr_ex)
+inline void
+describe_needs_terms(const char* what, uint32_t r, uint32_t count, char* msg,
+                     size_t cap)
+{
+  snprintf(msg, cap,
+           "%s: row %u is empty (%u empty rows, ST_CSR_EMPTY_ROWS_OK): its row "
+           "sum would be divided by zero; such a matrix is solved with "
+           "low-rank terms (st_solve_csr_terms)", what, r, count);
+}
+
+// the flagged create needs one entry: redirected loads read entry 0
+inline int
+check_nnz_min(uint64_t nnz, char* msg, size_t cap)
+{
+  if (nnz == 0) {
+    snprintf(msg, cap, "csr: nnz must be >= 1, got 0: loads past a row's end "
+                       "are redirected to entry 0");
+    return -1;
+  }
   return 0;
 }
 
@@ -115,9 +163,9 @@ check_col_idx(const int64_t* row_ptr, const int32_t* col_idx, uint32_t n,
 // Returns the number of non-empty classes.
 inline int
 plan(const int64_t* row_ptr, uint32_t n, uint32_t* order_out,
-     uint32_t* class_first, char* msg, size_t cap)
+     uint32_t* class_first, char* msg, size_t cap, bool empty_ok = false)
 {
-  if (check_row_ptr(row_ptr, n, false, 0, msg, cap))
+  if (check_row_ptr(row_ptr, n, false, 0, msg, cap, empty_ok))
     return -1;
   uint32_t count[kClasses] = { 0, 0, 0, 0 };
   for (uint32_t r = 0; r < n; r++)
@@ -139,7 +187,8 @@ plan(const int64_t* row_ptr, uint32_t n, uint32_t* order_out,
 // row_ptr on its own, then the column indices
 inline int
 check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
-           const int32_t* col_idx, const void* vals, char* msg, size_t cap)
+           const int32_t* col_idx, const void* vals, char* msg, size_t cap,
+           bool empty_ok = false)
 {
   if (dtype != 0 && dtype != 1) {
     snprintf(msg, cap, "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
@@ -149,13 +198,105 @@ check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
     snprintf(msg, cap, "csr: n must be in [1, 2^31), got %u", n);
     return -1;
   }
+  if (empty_ok && check_nnz_min(nnz, msg, cap)) // arrays of no entry may be null
+    return -1;
   if (!row_ptr || !col_idx || !vals) {
     snprintf(msg, cap, "csr: null row_ptr / col_idx / vals");
     return -1;
   }
-  if (check_row_ptr(row_ptr, n, true, nnz, msg, cap))
+  if (check_row_ptr(row_ptr, n, true, nnz, msg, cap, empty_ok))
     return -1;
   return check_col_idx(row_ptr, col_idx, n, nnz, msg, cap);
+}
+
+// ---------------------------------------------------------------------------
+// Low-rank terms (st_csr_terms.hip): M = A + sum_j u_j w_j^T, j < K.  The
+// device check applies the same predicates in the same order - the lowest
+// (term, vector, index) with u before w - and prints through the same
+// describe_* functions.
+// ---------------------------------------------------------------------------
+inline int
+check_terms_count(uint32_t K, char* msg, size_t cap)
+{
+  if (K < 1 || K > kTermsMax) {
+    snprintf(msg, cap, "csr terms: K must be in [1, %u], got %u", kTermsMax, K);
+    return -1;
+  }
+  return 0;
+}
+
+// finite and >= 0 (NaN fails every comparison)
+template <typename T>
+inline bool
+term_entry_bad(T x)
+{
+  return !(x >= (T)0) || x - x != (T)0; // inf - inf is NaN
+}
+
+// which: 0 = u, 1 = w
+inline void
+describe_term_entry(uint32_t j, int which, uint32_t i, double x, char* msg,
+                    size_t cap)
+{
+  snprintf(msg, cap,
+           "csr terms: %s_%u[%u] = %g: every entry of a term vector must be "
+           "finite and >= 0", which ? "w" : "u", j, i, x);
+}
+
+inline void
+describe_term_row(uint32_t r, double s0, char* msg, size_t cap)
+{
+  snprintf(msg, cap,
+           "csr terms: row %u of A + Σ u wᵀ has no positive entry "
+           "(its sum is %g): it would be divided by zero", r, s0);
+}
+
+template <typename T>
+inline int
+check_terms_vectors(uint32_t n, uint32_t K, const T* const* u, const T* const* w,
+                    char* msg, size_t cap)
+{
+  for (uint32_t j = 0; j < K; j++)
+    for (int which = 0; which < 2; which++) {
+      const T* p = which ? w[j] : u[j];
+      if (!p) {
+        snprintf(msg, cap, "csr terms: null %s_%u", which ? "w" : "u", j);
+        return -1;
+      }
+      for (uint32_t i = 0; i < n; i++)
+        if (term_entry_bad<T>(p[i])) {
+          describe_term_entry(j, which, i, (double)p[i], msg, cap);
+          return -1;
+        }
+    }
+  return 0;
+}
+
+// every row of M needs a positive entry: s_0[r] = the row sum of A plus
+// sum_j u_j[r] (w_j . 1), finite and > 0 (summed in double here; the device
+// judges the s_0 its own K0 computes)
+template <typename T>
+inline int
+check_terms_rows(uint32_t n, const int64_t* row_ptr, const T* vals, uint32_t K,
+                 const T* const* u, const T* const* w, char* msg, size_t cap)
+{
+  double d[kTermsMax] = { 0, 0, 0, 0 };
+  for (uint32_t j = 0; j < K; j++)
+    for (uint32_t i = 0; i < n; i++)
+      d[j] += (double)w[j][i];
+  for (uint32_t r = 0; r < n; r++) {
+    double s = 0;
+    for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; e++)
+      s += (double)vals[e];
+    for (uint32_t j = 0; j < K; j++)
+      s += (double)u[j][r] * d[j];
+    const T st = (T)s;
+    if (!(st > (T)0) || st - st != (T)0) {
+      describe_term_row(r, (double)st, msg, cap);
+      return -1;
+    }
+  }
+  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -188,14 +329,18 @@ describe_empty_col(uint32_t c, char* msg, size_t cap)
 }
 
 // a counting sort; the outputs must not overlap the inputs
+// flags & kEmptyRowsOk: the source may have empty rows and empty columns (the
+// result then has empty rows)
 inline int
 transpose_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
                const int32_t* col_idx, const void* vals, int64_t* t_row_ptr,
-               int32_t* t_col_idx, void* t_vals, char* msg, size_t cap)
+               int32_t* t_col_idx, void* t_vals, char* msg, size_t cap,
+               uint32_t flags = 0)
 {
+  const bool empty_ok = (flags & kEmptyRowsOk) != 0;
   if (check_transpose_nnz(nnz, msg, cap)) // before any array is read
     return -1;
-  if (check_host(dtype, n, nnz, row_ptr, col_idx, vals, msg, cap))
+  if (check_host(dtype, n, nnz, row_ptr, col_idx, vals, msg, cap, empty_ok))
     return -1;
   if (!t_row_ptr || !t_col_idx || !t_vals) {
     snprintf(msg, cap, "csr transpose: null t_row_ptr / t_col_idx / t_vals");
@@ -206,7 +351,7 @@ transpose_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
   for (uint64_t e = 0; e < nnz; e++)
     t_row_ptr[(uint32_t)col_idx[e] + 1]++;
   for (uint32_t c = 0; c < n; c++) {
-    if (t_row_ptr[c + 1] == 0) { // the lowest one: nothing was added up yet
+    if (t_row_ptr[c + 1] == 0 && !empty_ok) { // the lowest: nothing added up yet
       describe_empty_col(c, msg, cap);
       return -1;
     }

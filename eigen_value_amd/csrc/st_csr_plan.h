@@ -27,21 +27,30 @@ csr_row_class(int64_t len)
 }
 
 // one row per lane: the row_ptr predicate of st_csr_host.h (row_bad), and
-// cnt[block][class] = the block's rows of each class
+// cnt[block][class] = the block's rows of each class.  empty != nullptr
+// (ST_CSR_EMPTY_ROWS_OK): a row of no entries is legal and of class 0;
+// *empty counts such rows (an integer count does not depend on the order of
+// its increments) and err[1] takes the lowest one.
 __global__ __launch_bounds__(kBlock) void
 k_csr_check_ptr(const int64_t* __restrict__ row_ptr, uint32_t n, uint64_t nnz,
-                uint32_t* __restrict__ cnt, unsigned long long* err)
+                uint32_t* __restrict__ cnt, unsigned long long* err,
+                uint32_t* empty)
 {
   const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   int cls = -1;
   if (r < n) {
     const int64_t a = row_ptr[r], b = row_ptr[r + 1];
-    const bool bad = (r == 0 && a != 0) || b <= a ||
+    const bool bad = (r == 0 && a != 0) || (empty ? b < a : b <= a) ||
                      (r == (uint64_t)n - 1 && (uint64_t)b != nnz);
     if (bad)
       atomicMin(&err[0], (unsigned long long)r);
-    else
+    else {
       cls = csr_row_class(b - a);
+      if (b == a) {
+        atomicMin(&err[1], (unsigned long long)r);
+        atomicAdd(empty, 1u);
+      }
+    }
   }
 #pragma unroll
   for (int c = 0; c < csr::kClasses; c++) {

@@ -96,11 +96,15 @@ overlap(const void* a, size_t na, const void* b, size_t nb)
 int
 csr_transpose_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
                    const int32_t* col_idx, const void* vals, int64_t* t_row_ptr,
-                   int32_t* t_col_idx, void* t_vals)
+                   int32_t* t_col_idx, void* t_vals, uint32_t flags)
 {
   char msg[384];
+  if ((flags & ~csr::kEmptyRowsOk) != 0) {
+    set_error("st_csr_transpose_host_ex: unknown flags %u", flags);
+    return -1;
+  }
   if (csr::transpose_host(dtype, n, nnz, row_ptr, col_idx, vals, t_row_ptr,
-                          t_col_idx, t_vals, msg, sizeof(msg))) {
+                          t_col_idx, t_vals, msg, sizeof(msg), flags)) {
     set_error("%s", msg);
     return -1;
   }
@@ -109,10 +113,13 @@ csr_transpose_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
 
 int
 csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
-              void* d_t_vals, hipStream_t stream, CsrHandle** out)
+              void* d_t_vals, hipStream_t stream, CsrHandle** out, uint32_t flags)
 {
   ST_REQUIRE(out, "st_csr_transpose: null output pointer");
   *out = nullptr;
+  ST_REQUIRE((flags & ~csr::kEmptyRowsOk) == 0,
+             "st_csr_transpose_ex: unknown flags %u", flags);
+  const bool empty_ok = (flags & csr::kEmptyRowsOk) != 0;
   char msg[384];
   if (csr::check_transpose_nnz(a->nnz, msg, sizeof(msg))) {
     set_error("%s", msg);
@@ -150,6 +157,7 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
   char* base = static_cast<char*>(mem.p);
   unsigned long long* d_err = reinterpret_cast<unsigned long long*>(base + lay.err);
   uint32_t* d_cf = reinterpret_cast<uint32_t*>(d_err + 2);
+  uint32_t* d_empty = d_cf + 5; // the result's empty rows (ST_CSR_EMPTY_ROWS_OK)
   uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + lay.cnt);
   uint32_t* d_bsum = reinterpret_cast<uint32_t*>(base + lay.bsum);
   uint32_t* d_dtot = reinterpret_cast<uint32_t*>(base + lay.dtot);
@@ -180,11 +188,13 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
     return -1;
   ST_CHECK(hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, stream));
   ST_CHECK(hipStreamSynchronize(stream));
-  if (err[0] != ~0ull) {
+  if (err[0] != ~0ull && !empty_ok) {
     csr::describe_empty_col((uint32_t)err[0], msg, sizeof(msg));
     set_error("%s", msg);
     return -1;
   }
+  if (err[0] != ~0ull) // an empty column is legal here: the plan's check is next
+    ST_CHECK(hipMemsetAsync(d_err, 0xff, 2 * sizeof(unsigned long long), stream));
   hipLaunchKernelGGL(dev::k_tr_top, dim3(1), dim3(kBlock), 0, stream, d_bsum,
                      lay.ncb);
   if (check_launch("tr_top"))
@@ -233,7 +243,9 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
 
   // 4. the plan of t_row_ptr, as csr_create builds it (the predicate again:
   // it fails only if the matrix changed under the handle)
-  if (launch_csr_check_ptr(d_t_row_ptr, n, nnz, d_pcnt, d_err, stream))
+  ST_CHECK(hipMemsetAsync(d_empty, 0, sizeof(uint32_t), stream));
+  if (launch_csr_check_ptr(d_t_row_ptr, n, nnz, d_pcnt, d_err, stream,
+                           empty_ok ? d_empty : nullptr))
     return -1;
   ST_CHECK(hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, stream));
   ST_CHECK(hipStreamSynchronize(stream));
@@ -241,10 +253,14 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
     const uint32_t r = (uint32_t)err[0];
     int64_t w[2];
     ST_CHECK(hipMemcpy(w, d_t_row_ptr + r, sizeof(w), hipMemcpyDeviceToHost));
-    csr::describe_row(r, w[0], w[1], n, nnz, msg, sizeof(msg));
+    csr::describe_row(r, w[0], w[1], n, nnz, msg, sizeof(msg), empty_ok);
     set_error("csr transpose: the matrix changed under its handle (%s)", msg);
     return -1;
   }
+  const uint32_t first_empty = err[1] != ~0ull ? (uint32_t)err[1] : n;
+  uint32_t empty_rows = 0;
+  if (empty_ok)
+    ST_CHECK(hipMemcpy(&empty_rows, d_empty, sizeof(uint32_t), hipMemcpyDeviceToHost));
   ST_CHECK(hipMemsetAsync(d_order, 0, sizeof(uint32_t) * (size_t)n, stream));
   if (launch_csr_plan(d_t_row_ptr, n, d_pcnt, d_cf, d_order, stream))
     return -1;
@@ -253,7 +269,7 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
   ST_CHECK(hipStreamSynchronize(stream));
   CsrHandle* h = nullptr;
   if (csr_make_handle(a->dtype, n, nnz, d_t_row_ptr, d_t_col_idx, d_t_vals,
-                      d_order, cf, &h))
+                      d_order, cf, &h, empty_rows, first_empty))
     return -1;
   order.p = nullptr; // the handle's now
   *out = h;
@@ -272,6 +288,17 @@ st_csr_transpose_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_pt
   st::clear_error();
   return st::csr_transpose_host(dtype, n, nnz, row_ptr, col_idx, vals, t_row_ptr,
                                 t_col_idx, t_vals);
+}
+
+int
+st_csr_transpose_host_ex(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
+                         const int32_t* col_idx, const void* vals,
+                         int64_t* t_row_ptr, int32_t* t_col_idx, void* t_vals,
+                         unsigned int flags)
+{
+  st::clear_error();
+  return st::csr_transpose_host(dtype, n, nnz, row_ptr, col_idx, vals, t_row_ptr,
+                                t_col_idx, t_vals, flags);
 }
 
 uint64_t

@@ -155,31 +155,73 @@ struct CsrHandle
   uint32_t* d_order;     // [n] row indices sorted by class
   uint32_t row_first[5]; // class starts in d_order
   uint32_t blk_first[5]; // class starts in the launch's workgroup range
+  // ST_CSR_EMPTY_ROWS_OK handles: the rows without an entry and the lowest
+  // one (n when none).  A handle with any is refused by whatever divides by
+  // a row sum of A alone (csr_refuse_empty).
+  uint32_t empty_rows;
+  uint32_t first_empty;
 };
 constexpr uint32_t kCsrMagic = 0x43535231u;
+// the operator A + sum_j u_j w_j^T (st_csr_terms.hip): validated term vectors
+// bound to their matrix handle.  The vectors stay the caller's.
+struct CsrTermsHandle
+{
+  uint32_t magic; // kCsrTermsMagic while alive
+  int dtype;
+  int device;
+  uint32_t n;
+  uint32_t K;
+  const CsrHandle* csr; // the matrix it was checked against
+  const void* u[4];
+  const void* w[4];
+};
+constexpr uint32_t kCsrTermsMagic = 0x43535454u;
+int csr_refuse_empty(const CsrHandle* h, const char* what); // -1 + error if it has empty rows
+// validates u / w on the device (one pass), then s_0 of the operator;
+// synchronises `stream`
+int csr_terms_create(const CsrHandle* h, uint32_t K, const void* const* d_u,
+                     const void* const* d_w, hipStream_t stream,
+                     CsrTermsHandle** out);
+int csr_terms_destroy(CsrTermsHandle* t);
+// null + error unless t is a live terms object made for h
+const CsrTermsHandle* as_csr_terms(const void* t, const CsrHandle* h, const char* what);
+// bytes of the round's scratch: dots [K] | partial [K][2048] | x [n]
+size_t csr_terms_scratch_bytes(uint32_t n, uint32_t K);
+size_t csr_terms_dots_bytes(uint32_t K); // the part before x
+// scratch: dots | partial (csr_terms_dots_bytes); x [n] apart
+int launch_csr_terms_rowsum(const CsrHandle* h, const CsrTermsHandle* t, void* s,
+                            void* dots_part, hipStream_t stream);
+int launch_csr_terms_round(const CsrHandle* h, const CsrTermsHandle* t,
+                           const void* s_prev, void* s_next, const void* v_prev,
+                           void* v_cur, void* x, void* dots_part, double eps,
+                           uint32_t k, uint32_t max_itr, uint32_t semantics,
+                           st_state* st, hipStream_t stream);
 // what is checked on the host before anything is enqueued: the flags of a
 // CSR solve, and a host-resident matrix (dtype, n, row_ptr, then col_idx)
 int csr_check_flags(const st_options* opt);
 int csr_check_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
-                   const int32_t* col_idx, const void* vals);
+                   const int32_t* col_idx, const void* vals, uint32_t flags = 0);
 // validates on the device (row_ptr first, col_idx only after it passed),
 // builds the plan; synchronises `stream`
 int csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
                const int32_t* d_col_idx, const void* d_vals, hipStream_t stream,
-               CsrHandle** out);
+               CsrHandle** out, uint32_t flags = 0);
 // the handle over checked arrays and their plan (d_order [n], which becomes
 // the handle's own; cf [5] the class starts on the host)
 int csr_make_handle(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
                     const int32_t* d_col_idx, const void* d_vals,
-                    uint32_t* d_order, const uint32_t* cf, CsrHandle** out);
+                    uint32_t* d_order, const uint32_t* cf, CsrHandle** out,
+                    uint32_t empty_rows = 0, uint32_t first_empty = 0);
 // the stable transposition (st_csr_transpose.hip): T(a) into the caller's
 // device arrays, which must not overlap a's, and a handle over them with its
 // plan; synchronises `stream`.  The host twin needs no GPU.
 int csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
-                  void* d_t_vals, hipStream_t stream, CsrHandle** out);
+                  void* d_t_vals, hipStream_t stream, CsrHandle** out,
+                  uint32_t flags = 0);
 int csr_transpose_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
                        const int32_t* col_idx, const void* vals,
-                       int64_t* t_row_ptr, int32_t* t_col_idx, void* t_vals);
+                       int64_t* t_row_ptr, int32_t* t_col_idx, void* t_vals,
+                       uint32_t flags = 0);
 int csr_destroy(CsrHandle* h);
 const CsrHandle* as_csr(const void* p, const char* what); // null + error if not one
 int launch_csr_rowsum(const CsrHandle* h, void* s, hipStream_t stream);
@@ -191,9 +233,11 @@ int launch_csr_round(const CsrHandle* h, const void* s_prev, void* s_next,
 // predicate over n rows (d_err[0] = the lowest offending row, d_cnt
 // [ceil(n / 256)][4] = the rows of each class per block) and, from d_cnt,
 // the plan (d_cf [5] class starts, d_order [n])
+// d_empty != nullptr (ST_CSR_EMPTY_ROWS_OK): empty rows are legal, counted
+// there (zeroed by the caller), d_err[1] = the lowest one
 int launch_csr_check_ptr(const int64_t* d_row_ptr, uint32_t n, uint64_t nnz,
                          uint32_t* d_cnt, unsigned long long* d_err,
-                         hipStream_t stream);
+                         hipStream_t stream, uint32_t* d_empty = nullptr);
 int launch_csr_plan(const int64_t* d_row_ptr, uint32_t n, uint32_t* d_cnt,
                     uint32_t* d_cf, uint32_t* d_order, hipStream_t stream);
 // a batch of sparse matrices in stacked CSR storage (st_csr_batch.hip),

@@ -37,6 +37,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "st_csr_host.h"
 #include "st_internal.h"
 
 namespace st {
@@ -316,13 +317,15 @@ resolve(const st_options* opt, Resolved* r)
 // of st_half.hip for K0 and the round (solve_device_half checks the options)
 // csr != nullptr: the matrix is that CSR handle (d_mat is not dereferenced) -
 // the same matrix-free loop with st_csr.hip's K0 and two-launch round, x in
-// the first (here unused) slot of the deferred ring
+// the first (here unused) slot of the deferred ring; with `terms` the
+// operator is A + sum_j u_j w_j^T (st_csr_terms.hip's K0 and three-launch
+// round, dots and partials in the flat scratch, unused here)
 template <typename T>
 int64_t
 solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
              T* eigen_val, uint32_t* iter_cnt, const st_options* opt,
              st_stats* stats, bool flush_matrix = true, int storage = 0,
-             const CsrHandle* csr = nullptr)
+             const CsrHandle* csr = nullptr, const CsrTermsHandle* terms = nullptr)
 {
   static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value,
                 "fp32 / fp64 vectors");
@@ -376,6 +379,8 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   const bool flat_k0 = storage == 0 && !csr && round_flat_pays(n, n, sizeof(T));
   if (flat_k0 && ensure_part(c, sizeof(T) * round_flat_scratch(n, n)))
     return -1;
+  if (terms && ensure_part(c, csr_terms_dots_bytes(terms->K)))
+    return -1;
   T* d_part = reinterpret_cast<T*>(c->d_part);
   // rounds per host flag check: the launches queued behind the stopping
   // round still run as gated no-ops, and a gated flat round is two launches
@@ -419,7 +424,8 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   }
   T* const s0 = defer ? ring_s[0] : s_buf[0];
   if (csr) { // K0 on the CSR matrix
-    if (launch_csr_rowsum(csr, s0, s))
+    if (terms ? launch_csr_terms_rowsum(csr, terms, s0, d_part, s)
+              : launch_csr_rowsum(csr, s0, s))
       return -1;
   } else if (storage != 0) { // K0 on the 16-bit matrix
     if constexpr (std::is_same<T, float>::value) {
@@ -459,7 +465,12 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
         ev.push_back(eb);
         (void)hipEventRecord(ea, s);
       }
-      if (csr) // launch k+1 evaluates round k
+      if (csr && terms) // launch k+1 evaluates round k
+        rc |= launch_csr_terms_round(csr, terms, s_buf[cur], s_buf[cur ^ 1],
+                                     vb[k & 1], vb[(k + 1) & 1], ring_s[0], d_part,
+                                     o.eps, k + 1, o.max_itr, o.semantics,
+                                     c->d_state, s);
+      else if (csr)
         rc |= launch_csr_round(csr, s_buf[cur], s_buf[cur ^ 1], vb[k & 1],
                                vb[(k + 1) & 1], ring_s[0], o.eps, k + 1,
                                o.max_itr, o.semantics, c->d_state, s);
@@ -653,9 +664,11 @@ solve_host_half(Context* c, int storage, const void* mat, uint32_t n,
 int64_t
 solve_csr(Context* c, const CsrHandle* h, void* d_v_out, void* v_host,
           void* eigen_val, uint32_t* iter_cnt, const st_options* opt,
-          st_stats* stats)
+          st_stats* stats, const CsrTermsHandle* terms = nullptr)
 {
   if (csr_check_flags(opt))
+    return -1;
+  if (!terms && csr_refuse_empty(h, "st_solve_csr"))
     return -1;
   ST_REQUIRE(c, "null queue");
   ST_REQUIRE(c->device == h->device,
@@ -668,12 +681,119 @@ solve_csr(Context* c, const CsrHandle* h, void* d_v_out, void* v_host,
                                 static_cast<double*>(d_v_out),
                                 static_cast<double*>(v_host),
                                 static_cast<double*>(eigen_val), iter_cnt, opt,
-                                stats, false, 0, h);
+                                stats, false, 0, h, terms);
   return solve_device<float>(c, static_cast<float*>(tag), h->n,
                              static_cast<float*>(d_v_out),
                              static_cast<float*>(v_host),
                              static_cast<float*>(eigen_val), iter_cnt, opt,
-                             stats, false, 0, h);
+                             stats, false, 0, h, terms);
+}
+
+// The host-pointer solve of A + sum_j u_j w_j^T: everything validated on the
+// host first (dtype, flags, the matrix, K, the vectors u before w term by
+// term, then the rows of the operator); the workspace holds
+// [row_ptr | vals | col_idx | u_0 | w_0 | u_1 | ...]
+template <typename T>
+int
+check_terms_host_t(uint32_t n, const int64_t* row_ptr, const void* vals, uint32_t K,
+                   const void* const* u, const void* const* w)
+{
+  char msg[384];
+  const T* uu[csr::kTermsMax] = {};
+  const T* ww[csr::kTermsMax] = {};
+  for (uint32_t j = 0; j < K; j++) {
+    uu[j] = static_cast<const T*>(u[j]);
+    ww[j] = static_cast<const T*>(w[j]);
+  }
+  if (csr::check_terms_vectors<T>(n, K, uu, ww, msg, sizeof(msg)) ||
+      csr::check_terms_rows<T>(n, row_ptr, static_cast<const T*>(vals), K, uu, ww,
+                               msg, sizeof(msg))) {
+    set_error("%s", msg);
+    return -1;
+  }
+  return 0;
+}
+
+int64_t
+solve_host_csr_terms(Context* c, int dtype, uint32_t n, uint64_t nnz,
+                     const int64_t* row_ptr, const int32_t* col_idx,
+                     const void* vals, uint32_t K, const void* const* u,
+                     const void* const* w, uint32_t flags, void* eigen_val,
+                     void* eigen_vec, uint32_t* iter_cnt, const st_options* opt,
+                     st_stats* stats)
+{
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  if (csr_check_flags(opt))
+    return -1;
+  ST_REQUIRE((flags & ~csr::kEmptyRowsOk) == 0,
+             "max_eigen_value_csr_terms_ex: unknown flags %u", flags);
+  if (csr_check_host(dtype, n, nnz, row_ptr, col_idx, vals, flags))
+    return -1;
+  {
+    char msg[384];
+    if (csr::check_terms_count(K, msg, sizeof(msg))) {
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  ST_REQUIRE(u && w, "csr terms: null vector table");
+  if (dtype ? check_terms_host_t<double>(n, row_ptr, vals, K, u, w)
+            : check_terms_host_t<float>(n, row_ptr, vals, K, u, w))
+    return -1;
+  ST_REQUIRE(eigen_val && eigen_vec && iter_cnt, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  const size_t elem = dtype ? 8 : 4;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
+               b_col = up(4 * nnz), b_vec = up(elem * (size_t)n);
+  if (ensure_matrix(c, b_ptr + b_val + b_col + 2 * K * b_vec))
+    return -1;
+  char* base = static_cast<char*>(c->d_mat);
+  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
+  void* d_val = base + b_ptr;
+  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  const void* d_u[csr::kTermsMax] = {};
+  const void* d_w[csr::kTermsMax] = {};
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
+                          hipMemcpyHostToDevice, c->stream));
+  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  for (uint32_t j = 0; j < K; j++) {
+    char* at = base + b_ptr + b_val + b_col + 2 * j * b_vec;
+    ST_CHECK(hipMemcpyAsync(at, u[j], elem * (size_t)n, hipMemcpyHostToDevice,
+                            c->stream));
+    ST_CHECK(hipMemcpyAsync(at + b_vec, w[j], elem * (size_t)n,
+                            hipMemcpyHostToDevice, c->stream));
+    d_u[j] = at;
+    d_w[j] = at + b_vec;
+  }
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  CsrHandle* h = nullptr;
+  if (csr_create(dtype, n, nnz, d_ptr, d_col, d_val, c->stream, &h, flags))
+    return -1;
+  CsrTermsHandle* t = nullptr;
+  if (csr_terms_create(h, K, d_u, d_w, c->stream, &t)) {
+    (void)csr_destroy(h);
+    return -1;
+  }
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  const int64_t rc =
+    solve_csr(c, h, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local, t);
+  (void)csr_terms_destroy(t);
+  (void)csr_destroy(h);
+  if (rc < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
 }
 
 // the context's cached device workspace holds the three arrays of a host
@@ -1442,7 +1562,7 @@ solve_vbatched_host(Context* c, const T* mats, const uint32_t* dims,
 int
 csr_create_on(Context* c, int dtype, uint32_t n, uint64_t nnz,
               const int64_t* d_row_ptr, const int32_t* d_col_idx,
-              const void* d_vals, void** out)
+              const void* d_vals, void** out, uint32_t flags = 0)
 {
   ST_REQUIRE(out, "st_csr_create: null output pointer");
   *out = nullptr;
@@ -1450,15 +1570,35 @@ csr_create_on(Context* c, int dtype, uint32_t n, uint64_t nnz,
   if (ensure_device(c))
     return -1;
   CsrHandle* h = nullptr;
-  if (csr_create(dtype, n, nnz, d_row_ptr, d_col_idx, d_vals, c->stream, &h))
+  if (csr_create(dtype, n, nnz, d_row_ptr, d_col_idx, d_vals, c->stream, &h, flags))
     return -1;
   *out = h;
   return 0;
 }
 
 int
+csr_terms_create_on(Context* c, const CsrHandle* h, uint32_t K,
+                    const void* const* d_u, const void* const* d_w, void** out)
+{
+  ST_REQUIRE(out, "st_csr_terms_create: null output pointer");
+  *out = nullptr;
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  ST_REQUIRE(c->device == h->device,
+             "csr terms: the matrix lives on device %d, the queue on %d",
+             h->device, c->device);
+  CsrTermsHandle* t = nullptr;
+  if (csr_terms_create(h, K, d_u, d_w, c->stream, &t))
+    return -1;
+  *out = t;
+  return 0;
+}
+
+int
 csr_transpose_on(Context* c, const CsrHandle* a, int64_t* d_t_row_ptr,
-                 int32_t* d_t_col_idx, void* d_t_vals, void** out)
+                 int32_t* d_t_col_idx, void* d_t_vals, void** out,
+                 uint32_t flags = 0)
 {
   ST_REQUIRE(out, "st_csr_transpose: null output pointer");
   *out = nullptr;
@@ -1469,7 +1609,7 @@ csr_transpose_on(Context* c, const CsrHandle* a, int64_t* d_t_row_ptr,
              "csr transpose: the matrix lives on device %d, the queue on %d",
              a->device, c->device);
   CsrHandle* h = nullptr;
-  if (csr_transpose(a, d_t_row_ptr, d_t_col_idx, d_t_vals, c->stream, &h))
+  if (csr_transpose(a, d_t_row_ptr, d_t_col_idx, d_t_vals, c->stream, &h, flags))
     return -1;
   *out = h;
   return 0;
@@ -1519,7 +1659,7 @@ st_version(void)
   // the A/B probe switches the kernels were built with (st_kernels.hip):
   // "defaults" in every library build, the values in a probe build
   static const std::string v =
-    std::string("eigen_value_amd 0.5.0 (gfx950; probe switches: ") +
+    std::string("eigen_value_amd 0.6.0 (gfx950; probe switches: ") +
     st_probe_switches() + "; " + st::rccl_desc() + ")";
   return v.c_str();
 }
@@ -1752,6 +1892,94 @@ st_csr_create(void* wq, int dtype, uint32_t n, uint64_t nnz,
   st::DeviceGuard guard;
   return st::csr_create_on(st::as_ctx(wq), dtype, n, nnz, d_row_ptr, d_col_idx,
                            d_vals, out);
+}
+
+int
+st_csr_create_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                 const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                 const void* d_vals, unsigned int flags, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::csr_create_on(st::as_ctx(wq), dtype, n, nnz, d_row_ptr, d_col_idx,
+                           d_vals, out, flags);
+}
+
+int
+st_csr_empty_rows(void* csr, uint32_t* count, uint32_t* lowest)
+{
+  st::clear_error();
+  const st::CsrHandle* h = st::as_csr(csr, "st_csr_empty_rows");
+  if (!h)
+    return -1;
+  if (count)
+    *count = h->empty_rows;
+  if (lowest)
+    *lowest = h->first_empty;
+  return 0;
+}
+
+int
+st_csr_terms_create(void* wq, void* csr, uint32_t K, const void* const* d_u,
+                    const void* const* d_w, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (out)
+    *out = nullptr;
+  const st::CsrHandle* h = st::as_csr(csr, "st_csr_terms_create");
+  if (!h)
+    return -1;
+  return st::csr_terms_create_on(st::as_ctx(wq), h, K, d_u, d_w, out);
+}
+
+int64_t
+st_solve_csr_terms(void* wq, void* csr, void* terms, void* d_eigen_vec,
+                   void* eigen_vec_host, void* eigen_val, unsigned int* iter_cnt,
+                   const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  const st::CsrHandle* h = st::as_csr(csr, "st_solve_csr_terms");
+  if (!h)
+    return -1;
+  const st::CsrTermsHandle* t = st::as_csr_terms(terms, h, "st_solve_csr_terms");
+  if (!t)
+    return -1;
+  return st::solve_csr(st::as_ctx(wq), h, d_eigen_vec, eigen_vec_host, eigen_val,
+                       iter_cnt, opt, stats, t);
+}
+
+int64_t
+max_eigen_value_csr_terms_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                             const int64_t* row_ptr, const int32_t* col_idx,
+                             const void* vals, uint32_t K, const void* const* u,
+                             const void* const* w, unsigned int flags,
+                             void* eigen_val, void* eigen_vec,
+                             unsigned int* iter_cnt, const st_options* opt,
+                             st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_csr_terms(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
+                                  vals, K, u, w, flags, eigen_val, eigen_vec,
+                                  iter_cnt, opt, stats);
+}
+
+int
+st_csr_transpose_ex(void* wq, void* csr, int64_t* d_t_row_ptr,
+                    int32_t* d_t_col_idx, void* d_t_vals, unsigned int flags,
+                    void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (out)
+    *out = nullptr;
+  const st::CsrHandle* a = st::as_csr(csr, "st_csr_transpose_ex");
+  if (!a)
+    return -1;
+  return st::csr_transpose_on(st::as_ctx(wq), a, d_t_row_ptr, d_t_col_idx,
+                              d_t_vals, out, flags);
 }
 
 int64_t

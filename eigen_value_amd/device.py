@@ -261,12 +261,23 @@ class CsrMatrix:
 
     ``transpose()`` gives T(A) as a new ``CsrMatrix`` (``st_csr_transpose``: a
     stable sort of the entries by column on the device); ``.T`` is the same,
-    built once, kept, and closed with this matrix."""
+    built once, kept, and closed with this matrix.
+
+    ``allow_empty_rows`` (``st_csr_create_ex``, ``ST_CSR_EMPTY_ROWS_OK``): rows
+    without an entry are legal; ``empty_rows`` counts them and ``first_empty``
+    is the lowest (n when none).  Such a matrix is solved with ``CsrTerms``
+    (``solve_csr(m, terms)``, ``pagerank``); ``solve_csr(m)`` alone refuses
+    it, naming the row."""
 
     _t = None
+    allow_empty_rows = False
+    empty_rows = 0
 
     def __init__(self, crow_indices, col_indices=None, values=None, n: Optional[int] = None,
-                 *, solver: Optional["DeviceSolver"] = None):
+                 *, solver: Optional["DeviceSolver"] = None, allow_empty_rows: bool = False):
+        if not isinstance(allow_empty_rows, bool):
+            raise TypeError("allow_empty_rows must be a bool, got "
+                            f"{type(allow_empty_rows).__name__}")
         torch = _torch()
         self.handle = ctypes.c_void_p()
         self.L = _lib.load()
@@ -295,12 +306,27 @@ class CsrMatrix:
         solver = solver or DeviceSolver(self.device)
         try:
             _lib.check(self.L.st_set_stream(solver.q, _stream(self.device)), "st_set_stream")
-            _lib.check(self.L.st_csr_create(solver.q, self.dtype_code, self.n, self.nnz,
-                                            _ptr(self.crow), _ptr(self.col), _ptr(self.values),
-                                            ctypes.byref(self.handle)), "st_csr_create")
+            if allow_empty_rows:
+                _lib.check(self.L.st_csr_create_ex(
+                    solver.q, self.dtype_code, self.n, self.nnz, _ptr(self.crow), _ptr(self.col),
+                    _ptr(self.values), _lib.ST_CSR_EMPTY_ROWS_OK, ctypes.byref(self.handle)),
+                    "st_csr_create_ex")
+            else:
+                _lib.check(self.L.st_csr_create(solver.q, self.dtype_code, self.n, self.nnz,
+                                                _ptr(self.crow), _ptr(self.col),
+                                                _ptr(self.values), ctypes.byref(self.handle)),
+                           "st_csr_create")
         finally:
             if own:
                 solver.close()
+        self.allow_empty_rows = allow_empty_rows
+        self._read_empty()
+
+    def _read_empty(self) -> None:
+        k, lo = ctypes.c_uint32(), ctypes.c_uint32()
+        _lib.check(self.L.st_csr_empty_rows(self.handle, ctypes.byref(k), ctypes.byref(lo)),
+                   "st_csr_empty_rows")
+        self.empty_rows, self.first_empty = int(k.value), int(lo.value)
 
     @property
     def dtype(self):
@@ -315,12 +341,17 @@ class CsrMatrix:
                    "st_csr_get_plan")
         return order, first
 
-    def transpose(self, solver: Optional["DeviceSolver"] = None) -> "CsrMatrix":
+    def transpose(self, solver: Optional["DeviceSolver"] = None,
+                  allow_empty: bool = False) -> "CsrMatrix":
         """T(A) (``st_csr_transpose``): the entries sorted by column, those of
         one column in storage order, in tensors torch allocates - bit for bit
         ``csr_transpose_host`` of the same arrays.  Raises ``EigenValueError``
         naming the lowest column without an entry (the transposed matrix
-        would have an empty row).  The result is independent of this matrix."""
+        would have an empty row) unless ``allow_empty``
+        (``st_csr_transpose_ex``): the result is then an empty-rows matrix.
+        The result is independent of this matrix."""
+        if not isinstance(allow_empty, bool):
+            raise TypeError(f"allow_empty must be a bool, got {type(allow_empty).__name__}")
         torch = _torch()
         if not self.handle.value:
             raise ValueError("the matrix is closed")
@@ -335,12 +366,19 @@ class CsrMatrix:
         solver = solver or DeviceSolver(self.device)
         try:
             _lib.check(self.L.st_set_stream(solver.q, _stream(self.device)), "st_set_stream")
-            _lib.check(self.L.st_csr_transpose(solver.q, self.handle, _ptr(t.crow), _ptr(t.col),
-                                               _ptr(t.values), ctypes.byref(t.handle)),
-                       "st_csr_transpose")
+            if allow_empty:
+                _lib.check(self.L.st_csr_transpose_ex(
+                    solver.q, self.handle, _ptr(t.crow), _ptr(t.col), _ptr(t.values),
+                    _lib.ST_CSR_EMPTY_ROWS_OK, ctypes.byref(t.handle)), "st_csr_transpose_ex")
+            else:
+                _lib.check(self.L.st_csr_transpose(solver.q, self.handle, _ptr(t.crow),
+                                                   _ptr(t.col), _ptr(t.values),
+                                                   ctypes.byref(t.handle)), "st_csr_transpose")
         finally:
             if own:
                 solver.close()
+        t.allow_empty_rows = allow_empty
+        t._read_empty()
         return t
 
     @property
@@ -366,10 +404,124 @@ class CsrMatrix:
             pass
 
 
-def csr_transpose_host(indptr, indices, data):
+def csr_transpose_host(indptr, indices, data, allow_empty: bool = False):
     """T(A) of host (numpy) CSR arrays by the library's host twin
-    (``st_csr_transpose_host``; no GPU): ``(t_indptr, t_indices, t_data)``."""
-    return _lib.csr_transpose_host(indptr, indices, data)
+    (``st_csr_transpose_host``; no GPU): ``(t_indptr, t_indices, t_data)``.
+    ``allow_empty``: empty rows and columns are legal
+    (``st_csr_transpose_host_ex``)."""
+    return _lib.csr_transpose_host(indptr, indices, data, allow_empty=allow_empty)
+
+
+class CsrTerms:
+    """The rank-one terms of the operator ``M = A + sum_j u_j w_j^T``
+    (``st_csr_terms_create``): ``u`` and ``w`` are [K, n] tensors or sequences
+    of K vectors [n] on the matrix's device and of its dtype, 1 <= K <=
+    ``ST_CSR_TERMS_MAX``, nonnegative and finite.  The vectors are kept alive
+    (contiguous copies are made only where needed).  Shapes, dtypes and
+    devices are checked here before any library call; the entries and the rows
+    of ``M`` on the device (``EigenValueError`` naming the term, the vector
+    and the index, or the row without a positive entry).  Bound to ``csr``:
+    every call refuses it with another matrix."""
+
+    def __init__(self, csr: CsrMatrix, u, w, *, solver: Optional["DeviceSolver"] = None):
+        torch = _torch()
+        if not isinstance(csr, CsrMatrix):
+            raise TypeError(f"a CsrMatrix required, got {type(csr).__name__}")
+        if not csr.handle.value:
+            raise ValueError("the matrix is closed")
+        self.handle = ctypes.c_void_p()
+        self.L = csr.L
+        self.K = _lib.check_terms_arg(u, w, csr.n)
+        for name, vs in (("u", u), ("w", w)):
+            for j, x in enumerate(vs):
+                if not isinstance(x, torch.Tensor):
+                    raise TypeError(f"terms: {name}_{j} must be a torch tensor, got "
+                                    f"{type(x).__name__}")
+                if x.dtype != csr.dtype:
+                    raise TypeError(f"terms: {name}_{j} is {x.dtype}, the matrix {csr.dtype}")
+                if x.device != csr.device:
+                    raise ValueError(f"terms: {name}_{j} on {x.device}, the matrix on "
+                                     f"{csr.device}")
+        self.csr = csr
+        self.u = [x.contiguous() for x in u]
+        self.w = [x.contiguous() for x in w]
+        self._left = None
+        pu = (ctypes.c_void_p * self.K)(*[_ptr(x) for x in self.u])
+        pw = (ctypes.c_void_p * self.K)(*[_ptr(x) for x in self.w])
+        own = solver is None
+        solver = solver or DeviceSolver(csr.device)
+        try:
+            _lib.check(self.L.st_set_stream(solver.q, _stream(csr.device)), "st_set_stream")
+            _lib.check(self.L.st_csr_terms_create(solver.q, csr.handle, self.K, pu, pw,
+                                                  ctypes.byref(self.handle)),
+                       "st_csr_terms_create")
+        finally:
+            if own:
+                solver.close()
+
+    def scratch(self):
+        """A fresh scratch tensor for ``csr_terms_rowsum`` / ``csr_terms_round``
+        (``st_csr_terms_scratch_bytes``)."""
+        torch = _torch()
+        nbytes = int(self.L.st_csr_terms_scratch_bytes(self.csr.n, self.K))
+        return torch.zeros(nbytes, dtype=torch.uint8, device=self.csr.device)
+
+    def dots(self, scratch):
+        """dots[K] as the last ``csr_terms_rowsum`` / ``csr_terms_round`` left
+        them at the start of ``scratch``."""
+        es = 8 if self.csr.dtype_code else 4
+        return scratch[:self.K * es].view(self.csr.dtype).clone()
+
+    def x(self, scratch):
+        """x = v_prev * s_prev as the last ``csr_terms_round`` left it."""
+        off = 256 + self.K * 2048 * 8
+        es = 8 if self.csr.dtype_code else 4
+        return scratch[off:off + self.csr.n * es].view(self.csr.dtype).clone()
+
+    def close(self) -> None:
+        if self._left is not None:
+            tt, at = self._left
+            self._left = None
+            tt.close()
+            at.close()
+        if self.handle is not None and self.handle.value:
+            self.L.st_csr_terms_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csr_terms_rowsum(csr: CsrMatrix, terms: CsrTerms, scratch, out=None):
+    """s_0 of ``A + sum u w^T`` (``st_csr_terms_rowsum``): launch 0 with
+    terms; ``terms.dots(scratch)`` is then w_j . 1."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(csr.n, dtype=csr.dtype, device=csr.device)
+    _check_cuda(out, scratch)
+    assert out.dtype == csr.dtype and out.numel() >= csr.n
+    _lib.check(_lib.load().st_csr_terms_rowsum(csr.handle, terms.handle, _ptr(out),
+                                               _ptr(scratch), _stream(csr.device)),
+               "csr_terms_rowsum")
+    return out
+
+
+def csr_terms_round(csr: CsrMatrix, terms: CsrTerms, s_prev, s_next, v_prev, v_cur, scratch,
+                    state, *, eps: float = 1e-3, k: int = 1, max_itr: int = _lib.ST_MAX_ITR,
+                    semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Launch k >= 1 on ``A + sum u w^T`` (``st_csr_terms_round``):
+    ``csr_mfree_round``'s contract in three launches; ``terms.dots(scratch)``
+    is then w_j . x and ``terms.x(scratch)`` x itself."""
+    _check_cuda(s_prev, s_next, v_prev, v_cur, scratch, state)
+    assert all(t.dtype == csr.dtype and t.numel() >= csr.n and t.is_contiguous()
+               for t in (s_prev, s_next, v_prev, v_cur))
+    _lib.check(_lib.load().st_csr_terms_round(
+        csr.handle, terms.handle, _ptr(s_prev), _ptr(s_next), _ptr(v_prev), _ptr(v_cur),
+        _ptr(scratch), float(eps), k, max_itr, semantics, _ptr(state), _stream(csr.device)),
+        "csr_terms_round")
 
 
 def csr_rowsum(csr: CsrMatrix, out=None):
@@ -843,7 +995,8 @@ class DeviceSolver:
         _lib.check(rc, "st_solve_device_half")
         return float(ev.value), v, int(it.value), stats.as_dict()
 
-    def solve_csr(self, csr: "CsrMatrix", *, eps: Optional[float] = None, max_itr: int = 0,
+    def solve_csr(self, csr: "CsrMatrix", terms: Optional["CsrTerms"] = None, *,
+                  eps: Optional[float] = None, max_itr: int = 0,
                   semantics: int = _lib.ST_SEM_SYCL, batch: int = 0, trace: bool = False,
                   time_kernels: bool = False, left: bool = False):
         """The matrix-free solve of a sparse ``CsrMatrix`` (``st_solve_csr``):
@@ -855,16 +1008,35 @@ class DeviceSolver:
         ``left=True`` gives the LEFT Perron vector (v A = λ v; for a
         row-stochastic P the stationary distribution is ``v / v.sum()``): the
         solve of ``csr.T``, which is made on the device at the first use and
-        kept - bit for bit the solve of a host-transposed copy."""
+        kept - bit for bit the solve of a host-transposed copy.
+
+        ``terms`` (a ``CsrTerms`` of ``csr``): the operator is ``A + sum_j u_j
+        w_j^T`` (``st_solve_csr_terms``) - the way to solve a reducible or
+        periodic matrix, or one with empty rows.  With ``left=True`` it is
+        ``A^T + sum_j w_j u_j^T``: A is transposed with ``allow_empty=True``
+        and the term vectors swap roles (made once per terms object, kept, and
+        closed with it)."""
         if not isinstance(left, bool):
             raise TypeError(f"left must be a bool, got {type(left).__name__}")
         torch = _torch()
         if not isinstance(csr, CsrMatrix):
             raise TypeError(f"a CsrMatrix required, got {type(csr).__name__} "
                             "(solve takes dense tensors)")
+        if terms is not None:
+            if not isinstance(terms, CsrTerms):
+                raise TypeError(f"terms must be a CsrTerms, got {type(terms).__name__}")
+            if terms.csr is not csr:
+                raise ValueError("terms were made for another matrix")
         if csr.device.index != (self.device.index if self.device.index is not None
                                 else torch.cuda.current_device()):
             raise ValueError(f"matrix on {csr.device}, solver context on {self.device}")
+        if left and terms is not None:
+            if terms._left is None:
+                at = csr.transpose(self, allow_empty=True)
+                terms._left = (CsrTerms(at, terms.w, terms.u, solver=self), at)
+            tt, at = terms._left
+            return self.solve_csr(at, tt, eps=eps, max_itr=max_itr, semantics=semantics,
+                                  batch=batch, trace=trace, time_kernels=time_kernels)
         if left:
             if csr._t is None:                     # csr.T, made on this solver's queue
                 csr._t = csr.transpose(self)
@@ -881,10 +1053,75 @@ class DeviceSolver:
         stats = _lib.st_stats()
         self._trace = (csr.n, csr.dtype)
         _lib.check(self.L.st_set_stream(self.q, _stream(csr.device)), "st_set_stream")
+        if terms is not None:
+            rc = self.L.st_solve_csr_terms(self.q, csr.handle, terms.handle, _ptr(v), None,
+                                           ctypes.byref(ev), ctypes.byref(it),
+                                           ctypes.byref(opt), ctypes.byref(stats))
+            _lib.check(rc, "st_solve_csr_terms")
+            return float(ev.value), v, int(it.value), stats.as_dict()
         rc = self.L.st_solve_csr(self.q, csr.handle, _ptr(v), None, ctypes.byref(ev),
                                  ctypes.byref(it), ctypes.byref(opt), ctypes.byref(stats))
         _lib.check(rc, "st_solve_csr")
         return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def pagerank(self, A: "CsrMatrix", alpha: float = 0.85, teleport=None, dangling=None,
+                 **solve_options):
+        """PageRank of a link graph, on the device throughout.  ``A`` is a
+        nonnegative link-weight ``CsrMatrix`` (row = source; rows without an
+        entry - dangling nodes - are legal with ``allow_empty_rows=True``).
+        Rows are normalised on the device (``st_csr_rowsum`` gives the
+        out-weights, torch scales the values by ``alpha``), the matrix is
+        transposed (``allow_empty=True``) and the Google matrix
+        ``G^T = alpha P^T + t ((1 - alpha) 1 + alpha [row of P empty])^T``
+        is solved as one term; a ``dangling`` distribution of its own makes it
+        two, ``t ((1 - alpha) 1)^T + dangling (alpha [row empty])^T``.
+        ``teleport`` / ``dangling``: nonnegative tensors [n] (normalised to
+        sum 1 here), uniform when None.  ``solve_options`` are
+        ``solve_csr``'s (eps, max_itr, semantics, batch, trace,
+        time_kernels).
+
+        Returns ``(pi with sum 1, λ, iterations, stats)``; λ is 1 up to
+        rounding."""
+        torch = _torch()
+        if not isinstance(A, CsrMatrix):
+            raise TypeError(f"a CsrMatrix required, got {type(A).__name__}")
+        alpha = float(alpha)
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f"alpha must be in (0, 1), got {alpha}")
+        if "left" in solve_options or "terms" in solve_options:
+            raise TypeError("pagerank builds its own terms and transposition")
+        n, dt, device = A.n, A.dtype, A.device
+
+        def dist(x, name):
+            if x is None:
+                return torch.full((n,), 1.0 / n, dtype=dt, device=device)
+            if not isinstance(x, torch.Tensor) or tuple(x.shape) != (n,):
+                raise ValueError(f"{name} must be a tensor of shape ({n},)")
+            x = x.to(device=device, dtype=dt)
+            return x / x.sum()
+
+        t = dist(teleport, "teleport")
+        out_w = csr_rowsum(A)                                 # 0 for a dangling node
+        empty = out_w == 0
+        lens = A.crow[1:] - A.crow[:-1]
+        scale = torch.where(empty, torch.ones_like(out_w), out_w)
+        vals = A.values * alpha / torch.repeat_interleave(scale, lens)
+        P = CsrMatrix(A.crow, A.col, vals, n, solver=self, allow_empty_rows=True)
+        Pt = P.transpose(self, allow_empty=True)
+        P.close()
+        one = torch.ones(n, dtype=dt, device=device)
+        ind = empty.to(dt)
+        if dangling is None:
+            u, w = [t], [(1.0 - alpha) * one + alpha * ind]
+        else:
+            u, w = [t, dist(dangling, "dangling")], [(1.0 - alpha) * one, alpha * ind]
+        terms = CsrTerms(Pt, u, w, solver=self)
+        try:
+            lam, v, it, stats = self.solve_csr(Pt, terms, **solve_options)
+        finally:
+            terms.close()
+            Pt.close()
+        return v / v.sum(), lam, it, stats
 
     def solve_csr_batched(self, batch: "CsrBatch", *, eps: Optional[float] = None,
                           max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,

@@ -228,7 +228,8 @@ class EigenValue:
                                  *, eps: Optional[float] = None, max_itr: int = 0,
                                  semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
                                  time_kernels: bool = False, trace_sums: bool = False,
-                                 left: bool = False):
+                                 left: bool = False, terms=None,
+                                 allow_empty_rows: bool = False):
         """The matrix-free solve of a nonnegative SPARSE matrix in CSR storage
         (``max_eigen_value_csr_ex``): ``indptr`` [n + 1], ``indices`` [nnz] and
         ``data`` [nnz] (float32 or float64) as in ``scipy.sparse.csr_matrix``;
@@ -246,9 +247,27 @@ class EigenValue:
         is refused by name.  For a row-stochastic matrix the stationary
         distribution is ``v / v.sum()``.
 
+        ``terms=(u, w)`` solves ``A + sum_j u_j w_j^T``
+        (``max_eigen_value_csr_terms_ex``): ``u`` and ``w`` are [K, n] arrays
+        or sequences of K vectors, 1 <= K <= 4, nonnegative and finite - how a
+        reducible or periodic matrix is made primitive.  ``allow_empty_rows``
+        (with terms only) accepts rows without an entry.  Everything is
+        validated on the host, the error naming the term, the vector and the
+        index, or the row of the operator without a positive entry.  With
+        ``left=True`` the arrays are transposed on the host first and the term
+        vectors swap roles.
+
         Returns ``(λ, v, ts_ms, iterations)`` in the dtype of ``data``."""
         if not isinstance(left, bool):
             raise TypeError(f"left must be a bool, got {type(left).__name__}")
+        if not isinstance(allow_empty_rows, bool):
+            raise TypeError("allow_empty_rows must be a bool, got "
+                            f"{type(allow_empty_rows).__name__}")
+        if terms is None and allow_empty_rows:
+            raise ValueError("allow_empty_rows needs terms: a row sum of the matrix alone "
+                             "would be divided by zero")
+        if terms is not None and (not isinstance(terms, (tuple, list)) or len(terms) != 2):
+            raise TypeError("terms must be a pair (u, w)")
         if indices is None:
             sp = indptr
             if hasattr(sp, "crow_indices"):          # a torch.sparse_csr tensor
@@ -287,6 +306,25 @@ class EigenValue:
         eigen_vec = np.empty(n, dtype=data.dtype)
         iter_cnt = np.zeros(1, dtype=np.uint32)
         dtype = _lib.DTYPE_F32 if data.dtype == np.float32 else _lib.DTYPE_F64
+        if terms is not None:
+            u, w = terms
+            K = _lib.check_terms_arg(u, w, n)
+            u = [np.ascontiguousarray(x, dtype=data.dtype) for x in u]
+            w = [np.ascontiguousarray(x, dtype=data.dtype) for x in w]
+            if left:
+                indptr, indices, data = _lib.csr_transpose_host(
+                    indptr, indices, data, self.so_lib, allow_empty=True)
+                u, w = w, u
+            pu = (ctypes.c_void_p * K)(*[x.ctypes.data for x in u])
+            pw = (ctypes.c_void_p * K)(*[x.ctypes.data for x in w])
+            ts = self.so_lib.max_eigen_value_csr_terms_ex(
+                self.sycl_q, dtype, n, len(data), indptr.ctypes.data, indices.ctypes.data,
+                data.ctypes.data, K, pu, pw,
+                _lib.ST_CSR_EMPTY_ROWS_OK if (allow_empty_rows or left) else 0,
+                eigen_val.ctypes.data, eigen_vec.ctypes.data, iter_cnt.ctypes.data,
+                ctypes.byref(opt), None)
+            _lib.check(ts, "max_eigen_value_csr_terms_ex", self.so_lib)
+            return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
         name = "max_eigen_value_csr_left_ex" if left else "max_eigen_value_csr_ex"
         ts = getattr(self.so_lib, name)(
             self.sycl_q, dtype, n, len(data), indptr.ctypes.data, indices.ctypes.data,

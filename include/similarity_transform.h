@@ -657,6 +657,98 @@ int64_t max_eigen_value_csr_batched_ex(void* wq, int dtype, uint32_t batch,
                                        const st_options* opt, st_stats* stats);
 
 /* ---------------------------------------------------------------------- */
+/* 3e. sparse (CSR) solve with low-rank terms and empty rows               */
+/* ---------------------------------------------------------------------- */
+
+/* The operator M = A + sum_{j < K} u_j w_j^T, 1 <= K <= ST_CSR_TERMS_MAX: A a
+ * st_csr_create / st_csr_create_ex handle, u_j and w_j dense DEVICE vectors
+ * [n] in the handle's dtype, nonnegative and finite.  No entry of M is
+ * stored: a round of st_solve_csr becomes
+ *   x      = v_prev * s_prev                      (k_csr_prep's pass)
+ *   d_j    = w_j . x                    j < K     (the same pass + k_csr_dots)
+ *   tot_r  = row r of A times x, in st_solve_csr's order (0 for an empty row)
+ *   tot_r  = fma(u_j[r], d_j, tot_r)    j = 0 .. K-1, in that order
+ *   s_next = tot_r / x[r];  v_cur[r] = v_prev[r] * (s_prev[r] / m)
+ * and launch 0 the same with x = 1.  Three launches per round, all gated on
+ * the state as st_csr_mfree_round's two; stop test, m, lambda, counts, both
+ * semantics, batches, tracing, timing as st_solve_csr.  With u_j = 0 every
+ * bit is st_solve_csr's.  This is how a reducible or periodic matrix (a link
+ * graph) is made primitive - the Google matrix alpha P^T + t ((1 - alpha) 1 +
+ * alpha [row of P empty])^T is one term.
+ *
+ * The order of a dot d_j is a function of n alone (not of K, the other terms,
+ * the matrix or timing): G = min(ceil(n / 256), 2048) workgroups of 256
+ * lanes; lane t of workgroup b takes i = b 256 + t + g G 256, g ascending, by
+ * fma from 0; wave_sum's tree over the 64 lanes of a wave; the four wave
+ * sums in wave order -> partial[j][b]; then one workgroup: lane t adds
+ * partial[j][t + 256 g], g ascending, from 0, the same tree, the same four
+ * adds -> dots[j].  No float atomics, no workgroup waits on another.
+ *
+ * Empty rows.  ST_CSR_EMPTY_ROWS_OK makes st_csr_create_ex accept rows without
+ * an entry (row_ptr must not decrease; nnz >= 1 stays required; such a row is
+ * of class 0) and st_csr_transpose_ex / st_csr_transpose_host_ex accept
+ * columns without one (the result then has empty rows).  Without the flag the
+ * _ex calls are the plain ones.  A handle with empty rows is refused, the
+ * lowest such row named, by whatever divides by a row sum of A alone:
+ * st_solve_csr, st_csr_mfree_round (and max_eigen_value_csr_ex refuses the
+ * arrays as before); the calls of this section take it. */
+#define ST_CSR_TERMS_MAX 4
+#define ST_CSR_EMPTY_ROWS_OK 1u
+int st_csr_create_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                     const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                     const void* d_vals, unsigned int flags, void** out);
+/* The handle's rows without an entry and the lowest one (n when none);
+ * either pointer may be NULL.  0 or negative. */
+int st_csr_empty_rows(void* csr, uint32_t* count, uint32_t* lowest);
+int st_csr_transpose_ex(void* wq, void* csr, int64_t* d_t_row_ptr,
+                        int32_t* d_t_col_idx, void* d_t_vals,
+                        unsigned int flags, void** out);
+int st_csr_transpose_host_ex(int dtype, uint32_t n, uint64_t nnz,
+                             const int64_t* row_ptr, const int32_t* col_idx,
+                             const void* vals, int64_t* t_row_ptr,
+                             int32_t* t_col_idx, void* t_vals,
+                             unsigned int flags);
+/* A terms object over K pairs of device vectors (d_u[j], d_w[j]: host arrays
+ * of K device pointers), which stay the caller's and must outlive it.
+ * Validation on the device, before anything else: one pass over the vectors
+ * - every entry finite and >= 0, the lowest offender in the order (term, u
+ * before w, index) named as "u_1[17]" - then launch 0 of the operator: every
+ * s_0[r] finite and > 0, else "row r of A + Σ u wᵀ has no positive entry" (a
+ * row of M with a positive entry stays positive for every positive x, so no
+ * round divides by zero).  The object is bound to `csr`: every call refuses
+ * it with another handle.  Runs on wq's stream; returns after it completed. */
+int st_csr_terms_create(void* wq, void* csr, uint32_t K,
+                        const void* const* d_u, const void* const* d_w,
+                        void** terms);
+int st_csr_terms_destroy(void* terms);
+/* Bytes of the scratch st_csr_terms_rowsum / st_csr_terms_round take (256-byte
+ * aligned): dots [K] at offset 0, the workgroup partials [K][2048] at 256, x
+ * [n] behind them; 0 for a bad n or K.  No GPU needed. */
+uint64_t st_csr_terms_scratch_bytes(uint32_t n, uint32_t K);
+/* "terms_max=4 dot_grid=2048 lanes=256 combine=one_workgroup
+ * launches_per_round=3 dots_offset=0 partial_offset=256".  What
+ * tools/bench_csr_terms.py measured with it is in DESIGN.md, "Low-rank terms
+ * and empty rows".  No GPU needed. */
+const char* st_csr_terms_shape_desc(void);
+/* st_solve_csr on the operator; the same arguments and conventions. */
+int64_t st_solve_csr_terms(void* wq, void* csr, void* terms, void* d_eigen_vec,
+                           void* eigen_vec_host, void* eigen_val,
+                           unsigned int* iter_cnt, const st_options* opt,
+                           st_stats* stats);
+/* The host-pointer twin (u, w: K host vectors each): validates ON THE HOST -
+ * dtype, opt's flags, `flags` (ST_CSR_EMPTY_ROWS_OK), the matrix, K, the
+ * vectors, the rows of the operator, same order and messages - copies in,
+ * solves, copies out.  Returns h2d + loop ms or negative. */
+int64_t max_eigen_value_csr_terms_ex(void* wq, int dtype, uint32_t n,
+                                     uint64_t nnz, const int64_t* row_ptr,
+                                     const int32_t* col_idx, const void* vals,
+                                     uint32_t K, const void* const* u,
+                                     const void* const* w, unsigned int flags,
+                                     void* eigen_val, void* eigen_vec,
+                                     unsigned int* iter_cnt,
+                                     const st_options* opt, st_stats* stats);
+
+/* ---------------------------------------------------------------------- */
 /* 4. step-level kernels (asynchronous on `stream`, a hipStream_t or NULL) */
 /* ---------------------------------------------------------------------- */
 
@@ -1025,6 +1117,20 @@ int st_csr_mfree_round(void* csr, const void* d_s_prev, void* d_s_next,
                        const void* d_v_prev, void* d_v_cur, void* d_x,
                        double eps, unsigned int k, unsigned int max_itr,
                        unsigned int semantics, st_state* d_state, void* stream);
+/* The same two steps on A + sum_j u_j w_j^T (section 3e; what
+ * st_solve_csr_terms runs): `terms` a st_csr_terms_create object of `csr`,
+ * d_scratch st_csr_terms_scratch_bytes(n, K) bytes, 256-byte aligned.  After
+ * either call dots[K] (w_j . 1 after the row sum, w_j . x after a round), in
+ * the handle's dtype, stands at the start of d_scratch, and x behind the
+ * partials.  st_csr_rowsum works on an empty-rows handle (such a row sums to
+ * 0); st_csr_mfree_round refuses one. */
+int st_csr_terms_rowsum(void* csr, void* terms, void* d_s, void* d_scratch,
+                        void* stream);
+int st_csr_terms_round(void* csr, void* terms, const void* d_s_prev,
+                       void* d_s_next, const void* d_v_prev, void* d_v_cur,
+                       void* d_scratch, double eps, unsigned int k,
+                       unsigned int max_itr, unsigned int semantics,
+                       st_state* d_state, void* stream);
 
 /* The batched sparse scheme, step by step (what st_solve_csr_batched runs);
  * `h` is a st_csr_batch_create handle, all vectors device [N] stacked,
