@@ -10,7 +10,7 @@ SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hi
             eigen_value_amd/csrc/st_multi.hip eigen_value_amd/csrc/st_rendezvous.hip \
             eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip \
             eigen_value_amd/csrc/st_csr_batch.hip eigen_value_amd/csrc/st_csr_transpose.hip \
-            eigen_value_amd/csrc/st_csr_terms.hip
+            eigen_value_amd/csrc/st_csr_terms.hip eigen_value_amd/csrc/st_csr_multi.hip
 OBJ     := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
@@ -23,7 +23,7 @@ HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/c
             eigen_value_amd/csrc/st_half.h eigen_value_amd/csrc/st_csr.h \
             eigen_value_amd/csrc/st_csr_host.h eigen_value_amd/csrc/st_csr_batch.h \
             eigen_value_amd/csrc/st_csr_plan.h eigen_value_amd/csrc/st_csr_transpose.h \
-            eigen_value_amd/csrc/st_csr_terms.h
+            eigen_value_amd/csrc/st_csr_terms.h eigen_value_amd/csrc/st_csr_multi.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 
@@ -71,8 +71,20 @@ csr_terms_sanitize: $(LIB) tests/cpp/csr_terms_sanitize.cpp eigen_value_amd/csrc
 	./build/csr_terms_sanitize build/csr_tables/table0.bin build/csr_tables/table1.bin \
 	  build/csr_tables/table2.bin
 
+# the host side of the multi-column solve (st_csr_host.h: the packing and the
+# per-column validation in its fixed order) under the host sanitizers, as
+# csr_terms_sanitize
+csr_multi_sanitize: $(LIB) tests/cpp/csr_multi_sanitize.cpp eigen_value_amd/csrc/st_csr_host.h
+	@mkdir -p build/csr_tables
+	$(PYTHON) tests/csr_cases.py build/csr_tables
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	  -fno-omit-frame-pointer -Ieigen_value_amd/csrc tests/cpp/csr_multi_sanitize.cpp \
+	  -o build/csr_multi_sanitize
+	./build/csr_multi_sanitize build/csr_tables/table0.bin build/csr_tables/table1.bin \
+	  build/csr_tables/table2.bin
+
 clean:
 	rm -rf build eigen_value_amd/lib
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean probe csr_terms_sanitize
+.PHONY: all oracle clean probe csr_terms_sanitize csr_multi_sanitize

@@ -364,6 +364,23 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_csr_terms_rowsum.restype = i32
     L.st_csr_terms_round.argtypes = [P, P, P, P, P, P, P, f64, u32, u32, u32, P, P]
     L.st_csr_terms_round.restype = i32
+    L.st_csr_multi_create.argtypes = [P, P, u32, u32, P, P, ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_multi_create.restype = i32
+    L.st_csr_multi_destroy.argtypes = [P]
+    L.st_csr_multi_destroy.restype = i32
+    L.st_csr_multi_scratch_bytes.argtypes = [u32, u32, u32]
+    L.st_csr_multi_scratch_bytes.restype = u64
+    L.st_csr_multi_shape_desc.argtypes = []
+    L.st_csr_multi_shape_desc.restype = ctypes.c_char_p
+    L.st_solve_csr_multi.argtypes = [P, P, P, P, P, P, P, P, P, P]
+    L.st_solve_csr_multi.restype = i64
+    L.max_eigen_value_csr_multi_ex.argtypes = [P, i32, u32, u64, P, P, P, u32, u32, P, P, u32,
+                                               P, P, P, P, P, P]
+    L.max_eigen_value_csr_multi_ex.restype = i64
+    L.st_csr_multi_rowsum.argtypes = [P, P, P, P, P]
+    L.st_csr_multi_rowsum.restype = i32
+    L.st_csr_multi_round.argtypes = [P, P, P, P, P, P, P, f64, u32, u32, u32, P, P, P]
+    L.st_csr_multi_round.restype = i32
     L.st_csr_batch_create.argtypes = [P, i32, u32, P, u64, P, P, P,
                                       ctypes.POINTER(ctypes.c_void_p)]
     L.st_csr_batch_create.restype = i32
@@ -517,6 +534,61 @@ def check_terms_arg(u, w, n: int):
             if shape != (n,):
                 raise ValueError(f"terms: {name}_{j} has shape {shape}, ({n},) required")
     return ku
+
+
+ST_CSR_MULTI_MAX = 8
+
+
+def csr_multi_cp(C: int) -> int:
+    """The packed width of C columns: the smallest of 2, 4, 8 that is >= C."""
+    return 2 if C <= 2 else 4 if C <= 4 else 8
+
+
+def csr_multi_shape(L: Optional[ctypes.CDLL] = None) -> dict:
+    """st_csr_multi_shape_desc as a dict (integers where they are, tuples of
+    integers for the comma-separated tables)."""
+    L = L or load()
+    out = {}
+    for item in L.st_csr_multi_shape_desc().decode().split():
+        k, v = item.split("=")
+        if "," in v:
+            out[k] = tuple(int(x) for x in v.split(","))
+        else:
+            out[k] = int(v) if v.isdigit() else v
+    return out
+
+
+def check_multi_terms_arg(u, w, n: int):
+    """What every Python front checks of a multi terms argument before any
+    library call: ``u`` and ``w`` are [C, K, n] arrays (or [C, n], K = 1, or
+    sequences of C entries ``check_terms_arg`` accepts), 1 <= C <=
+    ST_CSR_MULTI_MAX, the same K for every column.  Returns (C, K, u, w) with
+    u, w as lists of C lists of K vectors."""
+    try:
+        cu, cw = len(u), len(w)
+    except TypeError:
+        raise TypeError("multi terms: u and w must be [C, K, n] arrays or sequences of C "
+                        "term sets")
+    if cu != cw:
+        raise ValueError(f"multi terms: {cu} columns u but {cw} columns w")
+    if not 1 <= cu <= ST_CSR_MULTI_MAX:
+        raise ValueError(f"multi terms: C must be in [1, {ST_CSR_MULTI_MAX}], got {cu}")
+
+    def rows(x):
+        return [x] if len(getattr(x, "shape", ())) == 1 else list(x)
+
+    uu, ww = [rows(x) for x in u], [rows(x) for x in w]
+    K = None
+    for c in range(cu):
+        try:
+            k = check_terms_arg(uu[c], ww[c], n)
+        except (TypeError, ValueError) as e:
+            raise type(e)(f"column {c}: {e}") from None
+        if K is not None and k != K:
+            raise ValueError(f"multi terms: column {c} has {k} terms, column 0 has {K}: every "
+                             "column takes the same K (pad with u = 0)")
+        K = k
+    return cu, K, uu, ww
 
 
 def csr_transpose_shape(L: Optional[ctypes.CDLL] = None) -> dict:

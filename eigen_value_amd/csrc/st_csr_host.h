@@ -2,7 +2,8 @@
 // the row-class table, the plan (rows sorted by class) and the validation of
 // a host CSR matrix.  Plain C++ without any HIP, so that it also compiles
 // into a stand-alone program (tests/cpp/csr_sanitize.cpp and, for the empty
-// rows flag and the low-rank terms, tests/cpp/csr_terms_sanitize.cpp, run
+// rows flag and the low-rank terms, tests/cpp/csr_terms_sanitize.cpp, for the
+// multi-column packing and validation tests/cpp/csr_multi_sanitize.cpp, run
 // under the host sanitizers).  Included by st_csr.hip; not a public header.
 //
 // Every function returns 0 (or a count) on success and -1 on failure with
@@ -297,6 +298,120 @@ check_terms_rows(uint32_t n, const int64_t* row_ptr, const T* vals, uint32_t K,
     }
   }
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Many term sets on one matrix (st_csr_multi.hip): M_c = A + sum_j u_{c,j}
+// w_{c,j}^T, c < C <= kMultiMax, the same K for every column; the tables are
+// indexed [c * K + j].  Vectors are packed [n][CP], the column fastest, CP =
+// multi_cp(C); padding columns hold 1.  The device check applies the
+// predicates above per column and reports the lowest offender by (column,
+// then term, u before w, index; then the column's rows), the message the
+// single one with the column in front.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMultiMax = 8;
+
+// the packed width: the smallest of 2, 4, 8 that is >= C
+constexpr uint32_t
+multi_cp(uint32_t C)
+{
+  return C <= 2 ? 2u : C <= 4 ? 4u : 8u;
+}
+
+// launch shape of the multi row pass (no effect on any result): rows side by
+// side and entries in flight per lane for class c when a packed row of x is
+// row_bytes = CP * b bytes.  Up to 16 bytes the single pass's table (R * U =
+// 8); 32 bytes R * U = 4; 64 bytes R * U = 2 - the x rows in flight stay at 32
+// registers per lane.
+constexpr uint32_t
+multi_rows(int c, uint32_t row_bytes)
+{
+  return row_bytes <= 16 ? kRows[c]
+         : row_bytes == 32 ? (c == 0 ? 4u : c == 1 ? 2u : 1u)
+                           : (c <= 1 ? 2u : 1u);
+}
+constexpr uint32_t
+multi_unroll(int c, uint32_t row_bytes)
+{
+  return row_bytes <= 16 ? kUnroll[c]
+         : row_bytes == 32 ? (c == 0 ? 1u : c == 1 ? 2u : 4u)
+                           : (c <= 1 ? 1u : 2u);
+}
+
+inline int
+check_multi_count(uint32_t C, uint32_t K, char* msg, size_t cap)
+{
+  if (C < 1 || C > kMultiMax) {
+    snprintf(msg, cap, "csr multi: C must be in [1, %u], got %u", kMultiMax, C);
+    return -1;
+  }
+  if (K < 1 || K > kTermsMax) {
+    snprintf(msg, cap,
+             "csr multi: K must be in [1, %u], got %u%s", kTermsMax, K,
+             K == 0 ? ": without terms every column is the same solve" : "");
+    return -1;
+  }
+  return 0;
+}
+
+// "csr terms: <text>" -> "csr terms: column c: <text>"
+inline void
+put_column(uint32_t c, char* msg, size_t cap)
+{
+  char tmp[384];
+  snprintf(tmp, sizeof(tmp), "%s", msg);
+  const char* head = "csr terms: ";
+  size_t skip = 0;
+  while (head[skip] && tmp[skip] == head[skip])
+    skip++;
+  if (head[skip])
+    skip = 0;
+  snprintf(msg, cap, "csr terms: column %u: %s", c, tmp + skip);
+}
+
+inline void
+describe_multi_entry(uint32_t c, uint32_t j, int which, uint32_t i, double x,
+                     char* msg, size_t cap)
+{
+  describe_term_entry(j, which, i, x, msg, cap);
+  put_column(c, msg, cap);
+}
+
+inline void
+describe_multi_row(uint32_t c, uint32_t r, double s0, char* msg, size_t cap)
+{
+  describe_term_row(r, s0, msg, cap);
+  put_column(c, msg, cap);
+}
+
+// the whole validation in its fixed order: column after column, the
+// column's vectors (term, u before w, index), then its rows
+template <typename T>
+inline int
+check_multi_terms(uint32_t n, const int64_t* row_ptr, const T* vals, uint32_t C,
+                  uint32_t K, const T* const* u, const T* const* w, char* msg,
+                  size_t cap)
+{
+  for (uint32_t c = 0; c < C; c++)
+    if (check_terms_vectors<T>(n, K, u + (size_t)c * K, w + (size_t)c * K, msg, cap) ||
+        check_terms_rows<T>(n, row_ptr, vals, K, u + (size_t)c * K,
+                            w + (size_t)c * K, msg, cap)) {
+      put_column(c, msg, cap);
+      return -1;
+    }
+  return 0;
+}
+
+// dst [n][CP] <- the C dense vectors src[c * stride] (c < C), padding columns
+// filled with 1: the packed form of term j when src = table + j, stride = K
+template <typename T>
+inline void
+pack_columns(uint32_t n, uint32_t C, uint32_t CP, const T* const* src,
+             size_t stride, T* dst)
+{
+  for (uint64_t i = 0; i < n; i++)
+    for (uint32_t c = 0; c < CP; c++)
+      dst[i * CP + c] = c < C ? src[(size_t)c * stride][i] : (T)1;
 }
 
 // ---------------------------------------------------------------------------

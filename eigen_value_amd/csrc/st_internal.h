@@ -196,6 +196,54 @@ int launch_csr_terms_round(const CsrHandle* h, const CsrTermsHandle* t,
                            void* v_cur, void* x, void* dots_part, double eps,
                            uint32_t k, uint32_t max_itr, uint32_t semantics,
                            st_state* st, hipStream_t stream);
+// up to 8 operators A + sum_j u_{c,j} w_{c,j}^T on one matrix handle
+// (st_csr_multi.hip): the validated term vectors packed [K][n][CP], and the
+// packed vectors of the solve loop.  Everything is the object's own (one
+// allocation); one solve at a time runs on it.
+struct CsrMultiHandle
+{
+  uint32_t magic; // kCsrMultiMagic while alive
+  int dtype;
+  int device;
+  uint32_t n;
+  uint32_t C;  // columns
+  uint32_t K;  // terms per column
+  uint32_t CP; // packed width: 2, 4 or 8 >= C
+  const CsrHandle* csr; // the matrix it was checked against
+  void* mem;
+  void* u; // [K][n][CP]
+  void* w;
+  void* s[2]; // [n][CP]
+  void* v[2];
+  void* scratch;         // dots | partial | x (csr_multi_scratch_bytes)
+  uint32_t blk_first[5]; // class starts in the row pass's workgroup range
+};
+constexpr uint32_t kCsrMultiMagic = 0x4353524du;
+// validates on the device per column (the vectors, then s_0 of every M_c) and
+// packs; synchronises `stream`.  h_pu / h_pw != nullptr (the host twin, which
+// validated the vectors itself): packed host arrays [K][n][CP] copied in
+// instead of d_u / d_w
+int csr_multi_create(const CsrHandle* h, uint32_t C, uint32_t K,
+                     const void* const* d_u, const void* const* d_w,
+                     hipStream_t stream, CsrMultiHandle** out,
+                     const void* h_pu = nullptr, const void* h_pw = nullptr);
+int csr_multi_destroy(CsrMultiHandle* t);
+const CsrMultiHandle* as_csr_multi(const void* t, const CsrHandle* h, const char* what);
+// dots [C][K] | partial [C][K][2048] (csr_multi_dots_bytes, x [n][CP] behind)
+size_t csr_multi_scratch_bytes(uint32_t n, uint32_t C, uint32_t K);
+size_t csr_multi_dots_bytes(uint32_t C, uint32_t K);
+int launch_csr_multi_rowsum(const CsrHandle* h, const CsrMultiHandle* t, void* s,
+                            void* scratch, hipStream_t stream);
+int launch_csr_multi_round(const CsrHandle* h, const CsrMultiHandle* t,
+                           const void* s_prev, void* s_next, const void* v_prev,
+                           void* v_cur, void* scratch, double eps, uint32_t k,
+                           uint32_t max_itr, uint32_t semantics, st_state* states,
+                           uint32_t* finished, hipStream_t stream);
+struct CsrBatchResult;
+// out [C][n] <- each column's final v from v0 / v1 by the parity of its end
+int launch_csr_multi_collect(const CsrMultiHandle* t, const void* v0, const void* v1,
+                             void* out, const st_state* states, CsrBatchResult* res,
+                             hipStream_t stream);
 // what is checked on the host before anything is enqueued: the flags of a
 // CSR solve, and a host-resident matrix (dtype, n, row_ptr, then col_idx)
 int csr_check_flags(const st_options* opt);

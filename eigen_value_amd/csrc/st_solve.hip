@@ -1095,6 +1095,254 @@ solve_host_csr_batched(Context* c, int dtype, uint32_t batch,
   return (int64_t)(h2d + local.loop_ms);
 }
 
+// The solve of up to 8 operators A + sum_j u_{c,j} w_{c,j}^T on one matrix
+// (st_csr_multi_create): solve_csr_batched's host loop - one memset of the C
+// states and the finished counter, one fill of v, K0, then opt->batch rounds
+// per look at the mirrored counter - with st_csr_multi.hip's three launches
+// per round for all columns.  Every column keeps its own state and stops in
+// its own round; the collect kernel picks each eigenvector from the ping-pong
+// buffer its end's parity names.  The packed vectors are the object's own.
+template <typename T>
+int64_t
+solve_csr_multi_t(Context* c, const CsrHandle* h, const CsrMultiHandle* t, T* d_v_out,
+                  T* v_host, T* eigen_vals, uint32_t* iter_cnts, uint32_t* converged,
+                  const Resolved& o, st_stats* stats)
+{
+  const uint32_t C = t->C;
+  const size_t out_bytes = sizeof(T) * (size_t)h->n * C;
+  if (ensure_device(c) || ensure_bstate(c, C) || ensure_bsum(c, 256) ||
+      ensure_part(c, sizeof(CsrBatchResult) * (size_t)C))
+    return -1;
+  struct Freed
+  {
+    void* p = nullptr;
+    ~Freed()
+    {
+      if (p)
+        (void)hipFree(p);
+    }
+  } tmp_out; // host output only: the collected [C][n] lives for this call
+  if (!d_v_out) {
+    ST_CHECK(hipMalloc(&tmp_out.p, out_bytes));
+    d_v_out = static_cast<T*>(tmp_out.p);
+  }
+  CsrBatchResult* d_res = static_cast<CsrBatchResult*>(c->d_part);
+  hipStream_t s = c->stream;
+  const uint32_t per_check = o.batch ? o.batch : kDefaultBatch;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)C, s));
+  ST_CHECK(hipMemsetAsync(c->d_bcount, 0, sizeof(uint32_t), s));
+  if (launch_fill<T>(static_cast<T*>(t->v[0]), (uint64_t)h->n * t->CP, (T)1, s))
+    return -1;
+  if (launch_csr_multi_rowsum(h, t, t->s[0], t->scratch, s)) // K0
+    return -1;
+  uint32_t enqueued = 0, cur = 0, batch_no = 0;
+  bool done = false;
+  while (!done && enqueued < o.max_itr) {
+    const uint32_t b = (o.max_itr - enqueued) < per_check ? (o.max_itr - enqueued)
+                                                          : per_check;
+    for (uint32_t j = 0; j < b; j++) {
+      const uint32_t k = enqueued + j; // launch k+1 evaluates round k
+      if (launch_csr_multi_round(h, t, t->s[cur], t->s[cur ^ 1], t->v[k & 1],
+                                 t->v[(k + 1) & 1], t->scratch, o.eps, k + 1,
+                                 o.max_itr, o.semantics, c->d_bstate, c->d_bcount, s))
+        return -1;
+      cur ^= 1;
+    }
+    enqueued += b;
+    const int sl = batch_no & 1;
+    if (launch_count_mirror(c->d_bcount, &c->h_bcount[sl], s))
+      return -1;
+    ST_CHECK(hipEventRecord(c->ev_flag[sl], s));
+    // wait for the previous batch's count while this batch runs
+    if (batch_no > 0) {
+      ST_CHECK(hipEventSynchronize(c->ev_flag[sl ^ 1]));
+      done = c->h_bcount[sl ^ 1] >= C;
+    }
+    batch_no++;
+  }
+  if (launch_csr_multi_collect(t, t->v[0], t->v[1], d_v_out, c->d_bstate, d_res, s))
+    return -1;
+  ST_CHECK(hipStreamSynchronize(s));
+  CsrBatchResult res[csr::kMultiMax];
+  ST_CHECK(hipMemcpy(res, d_res, sizeof(CsrBatchResult) * (size_t)C,
+                     hipMemcpyDeviceToHost));
+  const double loop_ms = ms_since(t0);
+
+  const auto t1 = std::chrono::steady_clock::now();
+  uint32_t rounds = 0, all = 1;
+  for (uint32_t b = 0; b < C; b++) {
+    const CsrBatchResult& fin = res[b];
+    ST_REQUIRE(fin.done, "internal: column %u ended without done flag", b);
+    eigen_vals[b] = (T)fin.lambda;
+    iter_cnts[b] = fin.iters;
+    if (converged)
+      converged[b] = fin.stop;
+    rounds = fin.end > rounds ? fin.end : rounds;
+    all &= fin.stop;
+  }
+  if (v_host)
+    ST_CHECK(hipMemcpy(v_host, d_v_out, out_bytes, hipMemcpyDeviceToHost));
+  const double d2h_ms = ms_since(t1);
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->loop_ms = loop_ms;
+    stats->d2h_ms = d2h_ms;
+    stats->rounds = rounds;
+    stats->converged = all;
+    stats->fused_launches = enqueued;
+  }
+  return (int64_t)loop_ms;
+}
+
+int
+csr_multi_check_flags(const st_options* opt)
+{
+  const uint32_t flags = opt ? opt->flags : 0u;
+  constexpr uint32_t kNo = ST_FLAG_TIME_KERNELS | ST_FLAG_TRACE_SUMS |
+                           ST_FLAG_ROUND_LOOP | ST_FLAG_WRITE_EVERY_ROUND |
+                           ST_FLAG_BATCH_ROUNDS;
+  ST_REQUIRE((flags & kNo) == 0,
+             "csr multi solve: ST_FLAG_TIME_KERNELS, ST_FLAG_TRACE_SUMS, "
+             "ST_FLAG_ROUND_LOOP, ST_FLAG_WRITE_EVERY_ROUND and "
+             "ST_FLAG_BATCH_ROUNDS are not supported (flags = %u): the matrix is "
+             "read only and every round is the same three launches for all "
+             "columns", flags);
+  ST_REQUIRE(!opt || opt->semantics <= ST_SEM_MAINPY, "unknown semantics %u",
+             opt->semantics);
+  return 0;
+}
+
+int64_t
+solve_csr_multi(Context* c, const CsrHandle* h, const CsrMultiHandle* t, void* d_v_out,
+                void* v_host, void* eigen_vals, uint32_t* iter_cnts,
+                uint32_t* converged, const st_options* opt, st_stats* stats)
+{
+  if (csr_multi_check_flags(opt))
+    return -1;
+  ST_REQUIRE(c, "null queue");
+  ST_REQUIRE(c->device == h->device,
+             "csr multi solve: the matrix lives on device %d, the queue on %d",
+             h->device, c->device);
+  ST_REQUIRE(eigen_vals && iter_cnts, "null output pointer");
+  ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
+  Resolved o;
+  if (h->dtype ? resolve<double>(opt, &o) : resolve<float>(opt, &o))
+    return -1;
+  if (h->dtype)
+    return solve_csr_multi_t<double>(
+      c, h, t, static_cast<double*>(d_v_out), static_cast<double*>(v_host),
+      static_cast<double*>(eigen_vals), iter_cnts, converged, o, stats);
+  return solve_csr_multi_t<float>(
+    c, h, t, static_cast<float*>(d_v_out), static_cast<float*>(v_host),
+    static_cast<float*>(eigen_vals), iter_cnts, converged, o, stats);
+}
+
+// The host-pointer twin: everything validated on the host first (dtype,
+// flags, the matrix, C and K, then column after column the vectors and the
+// rows of M_c), the terms packed on the host (csr::pack_columns) and copied
+// in packed; the workspace holds [row_ptr | vals | col_idx].
+template <typename T>
+int
+multi_host_pack_t(uint32_t n, const int64_t* row_ptr, const void* vals, uint32_t C,
+                  uint32_t K, const void* const* u, const void* const* w,
+                  std::vector<unsigned char>* pu, std::vector<unsigned char>* pw)
+{
+  char msg[448];
+  const T* uu[csr::kMultiMax * csr::kTermsMax] = {};
+  const T* ww[csr::kMultiMax * csr::kTermsMax] = {};
+  for (uint32_t i = 0; i < C * K; i++) {
+    uu[i] = static_cast<const T*>(u[i]);
+    ww[i] = static_cast<const T*>(w[i]);
+  }
+  if (csr::check_multi_terms<T>(n, row_ptr, static_cast<const T*>(vals), C, K, uu, ww,
+                                msg, sizeof(msg))) {
+    set_error("%s", msg);
+    return -1;
+  }
+  const uint32_t CP = csr::multi_cp(C);
+  const size_t per = (size_t)n * CP;
+  pu->resize(sizeof(T) * per * K);
+  pw->resize(sizeof(T) * per * K);
+  for (uint32_t j = 0; j < K; j++) {
+    csr::pack_columns<T>(n, C, CP, uu + j, K, reinterpret_cast<T*>(pu->data()) + per * j);
+    csr::pack_columns<T>(n, C, CP, ww + j, K, reinterpret_cast<T*>(pw->data()) + per * j);
+  }
+  return 0;
+}
+
+int64_t
+solve_host_csr_multi(Context* c, int dtype, uint32_t n, uint64_t nnz,
+                     const int64_t* row_ptr, const int32_t* col_idx, const void* vals,
+                     uint32_t C, uint32_t K, const void* const* u,
+                     const void* const* w, uint32_t flags, void* eigen_vals,
+                     void* eigen_vecs, uint32_t* iter_cnts, uint32_t* converged,
+                     const st_options* opt, st_stats* stats)
+{
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  if (csr_multi_check_flags(opt))
+    return -1;
+  ST_REQUIRE((flags & ~csr::kEmptyRowsOk) == 0,
+             "max_eigen_value_csr_multi_ex: unknown flags %u", flags);
+  if (csr_check_host(dtype, n, nnz, row_ptr, col_idx, vals, flags))
+    return -1;
+  {
+    char msg[384];
+    if (csr::check_multi_count(C, K, msg, sizeof(msg))) {
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  ST_REQUIRE(u && w, "csr multi: null vector table");
+  std::vector<unsigned char> pu, pw;
+  if (dtype ? multi_host_pack_t<double>(n, row_ptr, vals, C, K, u, w, &pu, &pw)
+            : multi_host_pack_t<float>(n, row_ptr, vals, C, K, u, w, &pu, &pw))
+    return -1;
+  ST_REQUIRE(eigen_vals && eigen_vecs && iter_cnts, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  const size_t elem = dtype ? 8 : 4;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
+               b_col = up(4 * nnz);
+  if (ensure_matrix(c, b_ptr + b_val + b_col))
+    return -1;
+  char* base = static_cast<char*>(c->d_mat);
+  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
+  void* d_val = base + b_ptr;
+  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
+                          hipMemcpyHostToDevice, c->stream));
+  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  CsrHandle* h = nullptr;
+  if (csr_create(dtype, n, nnz, d_ptr, d_col, d_val, c->stream, &h, flags))
+    return -1;
+  CsrMultiHandle* t = nullptr;
+  if (csr_multi_create(h, C, K, nullptr, nullptr, c->stream, &t, pu.data(), pw.data())) {
+    (void)csr_destroy(h);
+    return -1;
+  }
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  const int64_t rc = solve_csr_multi(c, h, t, nullptr, eigen_vecs, eigen_vals,
+                                     iter_cnts, converged, opt, &local);
+  (void)csr_multi_destroy(t);
+  (void)csr_destroy(h);
+  if (rc < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
+}
+
 template <typename T>
 int64_t
 solve_host(Context* c, const T* mat, uint32_t n, T* eigen_val, T* eigen_vec,
@@ -1596,6 +1844,33 @@ csr_terms_create_on(Context* c, const CsrHandle* h, uint32_t K,
 }
 
 int
+csr_multi_create_on(Context* c, const CsrHandle* h, uint32_t C, uint32_t K,
+                    const void* const* d_u, const void* const* d_w, void** out)
+{
+  ST_REQUIRE(out, "st_csr_multi_create: null output pointer");
+  *out = nullptr;
+  {
+    char msg[384];
+    if (csr::check_multi_count(C, K, msg, sizeof(msg))) {
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  ST_REQUIRE(d_u && d_w, "csr multi: null vector table");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  ST_REQUIRE(c->device == h->device,
+             "csr multi: the matrix lives on device %d, the queue on %d",
+             h->device, c->device);
+  CsrMultiHandle* t = nullptr;
+  if (csr_multi_create(h, C, K, d_u, d_w, c->stream, &t))
+    return -1;
+  *out = t;
+  return 0;
+}
+
+int
 csr_transpose_on(Context* c, const CsrHandle* a, int64_t* d_t_row_ptr,
                  int32_t* d_t_col_idx, void* d_t_vals, void** out,
                  uint32_t flags = 0)
@@ -1964,6 +2239,53 @@ max_eigen_value_csr_terms_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
   return st::solve_host_csr_terms(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
                                   vals, K, u, w, flags, eigen_val, eigen_vec,
                                   iter_cnt, opt, stats);
+}
+
+int
+st_csr_multi_create(void* wq, void* csr, uint32_t C, uint32_t K,
+                    const void* const* d_u, const void* const* d_w, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (out)
+    *out = nullptr;
+  const st::CsrHandle* h = st::as_csr(csr, "st_csr_multi_create");
+  if (!h)
+    return -1;
+  return st::csr_multi_create_on(st::as_ctx(wq), h, C, K, d_u, d_w, out);
+}
+
+int64_t
+st_solve_csr_multi(void* wq, void* csr, void* multi, void* d_eigen_vecs,
+                   void* eigen_vecs_host, void* eigen_vals, unsigned int* iter_cnts,
+                   unsigned int* converged, const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  const st::CsrHandle* h = st::as_csr(csr, "st_solve_csr_multi");
+  if (!h)
+    return -1;
+  const st::CsrMultiHandle* t = st::as_csr_multi(multi, h, "st_solve_csr_multi");
+  if (!t)
+    return -1;
+  return st::solve_csr_multi(st::as_ctx(wq), h, t, d_eigen_vecs, eigen_vecs_host,
+                             eigen_vals, iter_cnts, converged, opt, stats);
+}
+
+int64_t
+max_eigen_value_csr_multi_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                             const int64_t* row_ptr, const int32_t* col_idx,
+                             const void* vals, uint32_t C, uint32_t K,
+                             const void* const* u, const void* const* w,
+                             unsigned int flags, void* eigen_vals, void* eigen_vecs,
+                             unsigned int* iter_cnts, unsigned int* converged,
+                             const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_csr_multi(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
+                                  vals, C, K, u, w, flags, eigen_vals, eigen_vecs,
+                                  iter_cnts, converged, opt, stats);
 }
 
 int

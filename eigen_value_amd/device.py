@@ -524,6 +524,132 @@ def csr_terms_round(csr: CsrMatrix, terms: CsrTerms, s_prev, s_next, v_prev, v_c
         "csr_terms_round")
 
 
+class CsrMultiTerms:
+    """C term sets on one matrix, ``M_c = A + sum_j u_cj w_cj^T``
+    (``st_csr_multi_create``): ``u`` and ``w`` are [C, K, n] tensors ([C, n]
+    means K = 1) or sequences of C entries ``CsrTerms`` accepts, 1 <= C <=
+    ``ST_CSR_MULTI_MAX``, the same K for every column (a column that needs
+    fewer terms pads with u = 0, which changes no bit).  The library packs its
+    own copies [n, CP] (``self.CP`` = 2, 4 or 8 >= C), so the vectors need not
+    be kept.  Shapes, dtypes and devices are checked here before any library
+    call; the entries and the rows of every ``M_c`` on the device
+    (``EigenValueError`` naming the column first).  Bound to ``csr``: every
+    call refuses it with another matrix."""
+
+    def __init__(self, csr: CsrMatrix, u, w, *, solver: Optional["DeviceSolver"] = None):
+        torch = _torch()
+        if not isinstance(csr, CsrMatrix):
+            raise TypeError(f"a CsrMatrix required, got {type(csr).__name__}")
+        if not csr.handle.value:
+            raise ValueError("the matrix is closed")
+        self.handle = ctypes.c_void_p()
+        self.L = csr.L
+        self.C, self.K, uu, ww = _lib.check_multi_terms_arg(u, w, csr.n)
+        self.CP = _lib.csr_multi_cp(self.C)
+        for name, cols in (("u", uu), ("w", ww)):
+            for c, vs in enumerate(cols):
+                for j, x in enumerate(vs):
+                    if not isinstance(x, torch.Tensor):
+                        raise TypeError(f"multi terms: column {c}: {name}_{j} must be a torch "
+                                        f"tensor, got {type(x).__name__}")
+                    if x.dtype != csr.dtype:
+                        raise TypeError(f"multi terms: column {c}: {name}_{j} is {x.dtype}, the "
+                                        f"matrix {csr.dtype}")
+                    if x.device != csr.device:
+                        raise ValueError(f"multi terms: column {c}: {name}_{j} on {x.device}, "
+                                         f"the matrix on {csr.device}")
+        self.csr = csr
+        fu = [x.contiguous() for vs in uu for x in vs]           # [c * K + j], alive for the call
+        fw = [x.contiguous() for vs in ww for x in vs]
+        pu = (ctypes.c_void_p * len(fu))(*[_ptr(x) for x in fu])
+        pw = (ctypes.c_void_p * len(fw))(*[_ptr(x) for x in fw])
+        own = solver is None
+        solver = solver or DeviceSolver(csr.device)
+        try:
+            _lib.check(self.L.st_set_stream(solver.q, _stream(csr.device)), "st_set_stream")
+            _lib.check(self.L.st_csr_multi_create(solver.q, csr.handle, self.C, self.K, pu, pw,
+                                                  ctypes.byref(self.handle)),
+                       "st_csr_multi_create")
+        finally:
+            if own:
+                solver.close()
+
+    def scratch(self):
+        """A fresh scratch tensor for ``csr_multi_rowsum`` / ``csr_multi_round``
+        (``st_csr_multi_scratch_bytes``)."""
+        torch = _torch()
+        nbytes = int(self.L.st_csr_multi_scratch_bytes(self.csr.n, self.C, self.K))
+        return torch.zeros(nbytes, dtype=torch.uint8, device=self.csr.device)
+
+    def packed(self, value: float = 1.0):
+        """A packed vector [n, CP] of the matrix's dtype filled with ``value``."""
+        torch = _torch()
+        return torch.full((self.csr.n, self.CP), value, dtype=self.csr.dtype,
+                          device=self.csr.device)
+
+    def new_states(self):
+        """C zeroed ``st_state`` ([C, 64] uint8) and the finished counter."""
+        torch = _torch()
+        return (torch.zeros((self.C, 64), dtype=torch.uint8, device=self.csr.device),
+                torch.zeros(1, dtype=torch.int32, device=self.csr.device))
+
+    def dots(self, scratch):
+        """dots [C, K] as the last ``csr_multi_rowsum`` / ``csr_multi_round``
+        left them at the start of ``scratch``."""
+        es = 8 if self.csr.dtype_code else 4
+        return scratch[:self.C * self.K * es].view(self.csr.dtype).clone().view(self.C, self.K)
+
+    def x(self, scratch):
+        """x [n, CP] = v_prev * s_prev as the last ``csr_multi_round`` left it."""
+        off = 256 + self.CP * self.K * 2048 * 8
+        es = 8 if self.csr.dtype_code else 4
+        return (scratch[off:off + self.csr.n * self.CP * es].view(self.csr.dtype).clone()
+                .view(self.csr.n, self.CP))
+
+    def close(self) -> None:
+        if self.handle is not None and self.handle.value:
+            self.L.st_csr_multi_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csr_multi_rowsum(csr: CsrMatrix, mterms: CsrMultiTerms, scratch, out=None):
+    """s_0 of every ``M_c``, packed [n, CP] (``st_csr_multi_rowsum``): column
+    c is ``csr_terms_rowsum``'s on that column's terms, bit for bit;
+    ``mterms.dots(scratch)`` is then w_cj . 1."""
+    if out is None:
+        out = mterms.packed()
+    _check_cuda(out, scratch)
+    assert out.dtype == csr.dtype and out.numel() >= csr.n * mterms.CP and out.is_contiguous()
+    _lib.check(_lib.load().st_csr_multi_rowsum(csr.handle, mterms.handle, _ptr(out),
+                                               _ptr(scratch), _stream(csr.device)),
+               "csr_multi_rowsum")
+    return out
+
+
+def csr_multi_round(csr: CsrMatrix, mterms: CsrMultiTerms, s_prev, s_next, v_prev, v_cur,
+                    scratch, states, finished, *, eps: float = 1e-3, k: int = 1,
+                    max_itr: int = _lib.ST_MAX_ITR, semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Launch k >= 1 of every ``M_c`` (``st_csr_multi_round``) on packed
+    vectors [n, CP]: one pass over the matrix for all columns, column c bit for
+    bit ``csr_terms_round``'s.  ``states``: [C, 64] uint8; ``finished``: one
+    int32 word.  A column whose state has ``end`` set and below k, and a
+    padding column, get no write."""
+    _check_cuda(s_prev, s_next, v_prev, v_cur, scratch, states, finished)
+    assert all(t.dtype == csr.dtype and t.numel() >= csr.n * mterms.CP and t.is_contiguous()
+               for t in (s_prev, s_next, v_prev, v_cur))
+    assert states.numel() >= 64 * mterms.C and states.is_contiguous()
+    _lib.check(_lib.load().st_csr_multi_round(
+        csr.handle, mterms.handle, _ptr(s_prev), _ptr(s_next), _ptr(v_prev), _ptr(v_cur),
+        _ptr(scratch), float(eps), k, max_itr, semantics, _ptr(states), _ptr(finished),
+        _stream(csr.device)), "csr_multi_round")
+
+
 def csr_rowsum(csr: CsrMatrix, out=None):
     """s[r] = the sum of row r's entries (``st_csr_rowsum``): launch 0 of the
     CSR matrix-free scheme."""
@@ -1122,6 +1248,113 @@ class DeviceSolver:
             terms.close()
             Pt.close()
         return v / v.sum(), lam, it, stats
+
+    def solve_csr_multi(self, csr: "CsrMatrix", mterms: "CsrMultiTerms", *,
+                        eps: Optional[float] = None, max_itr: int = 0,
+                        semantics: int = _lib.ST_SEM_SYCL, batch_rounds: int = 0):
+        """The solve of C operators on one matrix (``st_solve_csr_multi``): one
+        pass over the matrix per round for all columns, each stopping in its
+        own round with the bits ``solve_csr(csr, CsrTerms(...))`` gives it
+        alone.  ``batch_rounds``: rounds per host check (0 = 8).  Returns (λ:
+        numpy [C], V: tensor [C, n], iterations: uint32 numpy [C], converged:
+        uint32 numpy [C], stats: dict).  For ONE term set ``solve_csr`` is the
+        call to use."""
+        import numpy as np
+        torch = _torch()
+        if not isinstance(csr, CsrMatrix):
+            raise TypeError(f"a CsrMatrix required, got {type(csr).__name__}")
+        if not isinstance(mterms, CsrMultiTerms):
+            raise TypeError(f"mterms must be a CsrMultiTerms, got {type(mterms).__name__}")
+        if mterms.csr is not csr:
+            raise ValueError("the multi terms were made for another matrix")
+        if csr.device.index != (self.device.index if self.device.index is not None
+                                else torch.cuda.current_device()):
+            raise ValueError(f"matrix on {csr.device}, solver context on {self.device}")
+        C = mterms.C
+        v = torch.empty((C, csr.n), dtype=csr.dtype, device=csr.device)
+        lam = np.empty(C, dtype=np.float64 if csr.dtype_code else np.float32)
+        its = np.zeros(C, dtype=np.uint32)
+        conv = np.zeros(C, dtype=np.uint32)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch_rounds, _lib.ST_FLAG_MATRIX_FREE)
+        stats = _lib.st_stats()
+        _lib.check(self.L.st_set_stream(self.q, _stream(csr.device)), "st_set_stream")
+        rc = self.L.st_solve_csr_multi(self.q, csr.handle, mterms.handle, _ptr(v), None,
+                                       lam.ctypes.data, its.ctypes.data, conv.ctypes.data,
+                                       ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(rc, "st_solve_csr_multi")
+        return lam, v, its, conv, stats.as_dict()
+
+    def pagerank_multi(self, A: "CsrMatrix", alpha: float = 0.85, teleports=None,
+                       dangling=None, **solve_options):
+        """Personalised PageRank: ``pagerank`` of one link graph under many
+        teleport vectors, ``teleports`` a tensor [C, n] (any C >= 1, solved in
+        chunks of 8).  The graph is normalised and transposed ONCE; every chunk
+        is one ``solve_csr_multi``, one pass over the matrix per round for its
+        columns.  ``dangling`` (one distribution [n] for all columns, or None)
+        and ``alpha`` as in ``pagerank``; ``solve_options`` are
+        ``solve_csr_multi``'s (eps, max_itr, semantics, batch_rounds).
+
+        A teleport vector must be positive wherever a node has no in-link
+        (with ``dangling`` also: wherever the dangling distribution is zero
+        too), or that row of the operator has no positive entry: the
+        validation then names the column and the row.
+
+        Returns ``(Π [C, n], each row summing to 1, λ numpy [C], iterations
+        uint32 numpy [C], stats of the last chunk)``; row c is bit for bit
+        ``pagerank(A, alpha, teleport=teleports[c], dangling=dangling)``."""
+        import numpy as np
+        torch = _torch()
+        if not isinstance(A, CsrMatrix):
+            raise TypeError(f"a CsrMatrix required, got {type(A).__name__}")
+        alpha = float(alpha)
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f"alpha must be in (0, 1), got {alpha}")
+        n, dt, device = A.n, A.dtype, A.device
+        if (not isinstance(teleports, torch.Tensor) or teleports.dim() != 2
+                or teleports.shape[0] < 1 or teleports.shape[1] != n):
+            raise ValueError(f"teleports must be a tensor of shape (C, {n}), C >= 1")
+
+        def dist(x, name):
+            if not isinstance(x, torch.Tensor) or tuple(x.shape) != (n,):
+                raise ValueError(f"{name} must be a tensor of shape ({n},)")
+            x = x.to(device=device, dtype=dt)
+            return x / x.sum()
+
+        ts = [dist(teleports[c].contiguous(), f"teleports[{c}]")
+              for c in range(teleports.shape[0])]
+        dang = None if dangling is None else dist(dangling, "dangling")
+        out_w = csr_rowsum(A)                                 # 0 for a dangling node
+        empty = out_w == 0
+        lens = A.crow[1:] - A.crow[:-1]
+        scale = torch.where(empty, torch.ones_like(out_w), out_w)
+        vals = A.values * alpha / torch.repeat_interleave(scale, lens)
+        P = CsrMatrix(A.crow, A.col, vals, n, solver=self, allow_empty_rows=True)
+        Pt = P.transpose(self, allow_empty=True)
+        P.close()
+        one = torch.ones(n, dtype=dt, device=device)
+        ind = empty.to(dt)
+        pis, lams, its, stats = [], [], [], {}
+        try:
+            for c0 in range(0, len(ts), _lib.ST_CSR_MULTI_MAX):
+                chunk = ts[c0:c0 + _lib.ST_CSR_MULTI_MAX]
+                if dang is None:
+                    u = [[t] for t in chunk]
+                    w = [[(1.0 - alpha) * one + alpha * ind]] * len(chunk)
+                else:
+                    u = [[t, dang] for t in chunk]
+                    w = [[(1.0 - alpha) * one, alpha * ind]] * len(chunk)
+                mt = CsrMultiTerms(Pt, u, w, solver=self)
+                try:
+                    lam, V, it, _, stats = self.solve_csr_multi(Pt, mt, **solve_options)
+                finally:
+                    mt.close()
+                pis += [V[c] / V[c].sum() for c in range(len(chunk))]
+                lams.append(lam)
+                its.append(it)
+        finally:
+            Pt.close()
+        return torch.stack(pis), np.concatenate(lams), np.concatenate(its), stats
 
     def solve_csr_batched(self, batch: "CsrBatch", *, eps: Optional[float] = None,
                           max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,

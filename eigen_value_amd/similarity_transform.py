@@ -333,6 +333,58 @@ class EigenValue:
         _lib.check(ts, name, self.so_lib)
         return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
 
+    def similarity_transform_csr_multi(self, indptr, indices=None, data=None, *, terms=None,
+                                       eps: Optional[float] = None, max_itr: int = 0,
+                                       semantics: int = _lib.ST_SEM_SYCL, batch_rounds: int = 0,
+                                       allow_empty_rows: bool = False):
+        """C operators on ONE sparse matrix, ``M_c = A + sum_j u_cj w_cj^T``
+        (``max_eigen_value_csr_multi_ex``): the matrix as
+        ``similarity_transform_csr`` takes it (arrays, a ``scipy.sparse``
+        matrix or a ``torch.sparse_csr`` tensor), ``terms=(U, W)`` with U, W
+        [C, K, n] arrays ([C, n] means K = 1), 1 <= C <= 8, 1 <= K <= 4.  One
+        pass over the matrix per round serves every column; each column gets
+        the bits ``similarity_transform_csr(..., terms=(U[c], W[c]))`` gives
+        it.  Everything is validated on the host, the error naming the column
+        first.  Returns ``(λ [C], V [C, n], ts_ms, iterations uint32 [C],
+        converged uint32 [C])`` in the dtype of ``data``."""
+        if not isinstance(allow_empty_rows, bool):
+            raise TypeError("allow_empty_rows must be a bool, got "
+                            f"{type(allow_empty_rows).__name__}")
+        if not isinstance(terms, (tuple, list)) or len(terms) != 2:
+            raise TypeError("terms must be a pair (U, W)")
+        if indices is None:
+            indptr, indices, data, _ = self._csr_triple(indptr)
+        data = np.ascontiguousarray(data)
+        assert data.dtype.num in (11, 12), "dtype of data must be float32 or float64 !"
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.asarray(indices)
+        assert indices.dtype.kind in "iu", "indices must be an integer array !"
+        if indices.size and (indices.min() < -2**31 or indices.max() >= 2**31):
+            raise _lib.EigenValueError("csr: a column index does not fit int32")
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        n = len(indptr) - 1
+        assert len(indices) == len(data), "indices and data must have one length !"
+        C, K, uu, ww = _lib.check_multi_terms_arg(terms[0], terms[1], n)
+        fu = [np.ascontiguousarray(x, dtype=data.dtype) for vs in uu for x in vs]
+        fw = [np.ascontiguousarray(x, dtype=data.dtype) for vs in ww for x in vs]
+        pu = (ctypes.c_void_p * len(fu))(*[x.ctypes.data for x in fu])
+        pw = (ctypes.c_void_p * len(fw))(*[x.ctypes.data for x in fw])
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch_rounds, _lib.ST_FLAG_MATRIX_FREE)
+        eigen_vals = np.empty(C, dtype=data.dtype)
+        eigen_vecs = np.empty((C, n), dtype=data.dtype)
+        iter_cnts = np.zeros(C, dtype=np.uint32)
+        converged = np.zeros(C, dtype=np.uint32)
+        dtype = _lib.DTYPE_F32 if data.dtype == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_csr_multi_ex(
+            self.sycl_q, dtype, n, len(data), indptr.ctypes.data, indices.ctypes.data,
+            data.ctypes.data, C, K, pu, pw,
+            _lib.ST_CSR_EMPTY_ROWS_OK if allow_empty_rows else 0,
+            eigen_vals.ctypes.data, eigen_vecs.ctypes.data, iter_cnts.ctypes.data,
+            converged.ctypes.data, ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_csr_multi_ex", self.so_lib)
+        return eigen_vals, eigen_vecs, int(ts), iter_cnts, converged
+
     @staticmethod
     def _csr_triple(m):
         """(indptr, indices, data, n) of one matrix of a sparse batch."""

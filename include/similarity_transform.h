@@ -749,6 +749,72 @@ int64_t max_eigen_value_csr_terms_ex(void* wq, int dtype, uint32_t n,
                                      const st_options* opt, st_stats* stats);
 
 /* ---------------------------------------------------------------------- */
+/* 3f. many term sets on one sparse matrix                                  */
+/* ---------------------------------------------------------------------- */
+
+/* C operators on ONE handle, M_c = A + sum_{j < K} u_{c,j} w_{c,j}^T, c < C,
+ * 1 <= C <= ST_CSR_MULTI_MAX, 1 <= K <= ST_CSR_TERMS_MAX terms for every
+ * column (a column that needs fewer pads with u = 0, which changes no bit; K
+ * = 0 is refused: every column would be the same solve) - personalised
+ * PageRank, one link graph under many teleport vectors.  One pass over the
+ * matrix per round serves all columns: the library keeps packed copies
+ * [n][CP] of s, v, x and [K][n][CP] of u, w, the column index fastest, CP =
+ * the smallest of 2, 4, 8 that is >= C, so one gather brings x[col] for every
+ * column.  Every column has its own st_state and stops in its own round, and
+ * its eigenvalue, eigenvector, count, converged flag and final state are bit
+ * for bit st_solve_csr_terms' on (A, u_{c,.}, w_{c,.}) alone, for both
+ * semantics, both dtypes and any max_itr.  No float atomics, no workgroup
+ * waits on another.  Not offered here: tracing and kernel timing, a left
+ * solve, batches, sharded or 16-bit storage, C > 8 in one call.
+ *
+ * st_csr_multi_create: d_u / d_w are host arrays of C * K device pointers,
+ * [c * K + j] = a dense vector [n] in the handle's dtype; they are read
+ * during the call only.  Validation on the device per column, the single
+ * object's predicates, the lowest offender by (column, then term, u before w,
+ * index; then the column's rows), the single message with the column in
+ * front: "column 2: u_1[17] = -0.5 ...", "column 2: row 9 of A + Σ u wᵀ has
+ * no positive entry".  The object is bound to `csr` (every call refuses it
+ * with another handle) and owns its packed vectors: one solve at a time. */
+#define ST_CSR_MULTI_MAX 8
+int st_csr_multi_create(void* wq, void* csr, uint32_t C, uint32_t K,
+                        const void* const* d_u, const void* const* d_w,
+                        void** multi);
+int st_csr_multi_destroy(void* multi);
+/* Bytes of the scratch st_csr_multi_rowsum / st_csr_multi_round take (256-byte
+ * aligned): dots [C][K] at offset 0, the workgroup partials [CP][K][2048] at
+ * 256, x [n][CP] behind them; 0 for a bad n, C or K.  No GPU needed. */
+uint64_t st_csr_multi_scratch_bytes(uint32_t n, uint32_t C, uint32_t K);
+/* "multi_max=8 terms_max=4 widths=2,4,8 dot_grid=2048 lanes=256
+ * combine=one_workgroup_per_column launches_per_round=3 dots_offset=0
+ * partial_offset=256 rows16=... unroll16=... rows32=... unroll32=... rows64=...
+ * unroll64=...": rowsB / unrollB are the rows side by side and the entries in
+ * flight per lane of the four row classes when a packed row is B = CP * b
+ * bytes.  What tools/bench_csr_multi.py measured with it is in DESIGN.md,
+ * "Many term sets on one matrix".  No GPU needed. */
+const char* st_csr_multi_shape_desc(void);
+/* st_solve_csr_batched's conventions: d_eigen_vecs device [C][n] (each column
+ * contiguous) and / or eigen_vecs_host, eigen_vals [C] in the handle's dtype,
+ * iter_cnts [C], converged [C] (may be NULL); opt->batch rounds (default 8)
+ * per host check of the count of finished columns. */
+int64_t st_solve_csr_multi(void* wq, void* csr, void* multi, void* d_eigen_vecs,
+                           void* eigen_vecs_host, void* eigen_vals,
+                           unsigned int* iter_cnts, unsigned int* converged,
+                           const st_options* opt, st_stats* stats);
+/* The host-pointer twin (u, w: C * K host vectors, [c * K + j]): validates ON
+ * THE HOST - dtype, opt's flags, `flags` (ST_CSR_EMPTY_ROWS_OK), the matrix, C
+ * and K, then column after column the vectors and the rows of M_c, same
+ * messages - packs on the host, copies in, solves, copies out. */
+int64_t max_eigen_value_csr_multi_ex(void* wq, int dtype, uint32_t n,
+                                     uint64_t nnz, const int64_t* row_ptr,
+                                     const int32_t* col_idx, const void* vals,
+                                     uint32_t C, uint32_t K,
+                                     const void* const* u, const void* const* w,
+                                     unsigned int flags, void* eigen_vals,
+                                     void* eigen_vecs, unsigned int* iter_cnts,
+                                     unsigned int* converged,
+                                     const st_options* opt, st_stats* stats);
+
+/* ---------------------------------------------------------------------- */
 /* 4. step-level kernels (asynchronous on `stream`, a hipStream_t or NULL) */
 /* ---------------------------------------------------------------------- */
 
@@ -1131,6 +1197,23 @@ int st_csr_terms_round(void* csr, void* terms, const void* d_s_prev,
                        void* d_scratch, double eps, unsigned int k,
                        unsigned int max_itr, unsigned int semantics,
                        st_state* d_state, void* stream);
+/* The same for the C operators of a st_csr_multi_create object (section 3f;
+ * what st_solve_csr_multi runs).  All vectors are PACKED device arrays
+ * [n][CP], aligned to a row of CP * b bytes; d_scratch
+ * st_csr_multi_scratch_bytes(n, C, K) bytes, 256-byte aligned; d_states device
+ * [C] (zero = fresh), d_finished one device word.  Column c of s_next, v_cur,
+ * x and dots[c][.] and d_states[c] are bit for bit st_csr_terms_rowsum's /
+ * st_csr_terms_round's on that column's terms alone.  A column whose state
+ * has `end` set and below k gets no write at all, nor does a padding column
+ * (C <= c < CP); the publisher of a round that sets a column's `end` adds 1
+ * to *d_finished. */
+int st_csr_multi_rowsum(void* csr, void* multi, void* d_s, void* d_scratch,
+                        void* stream);
+int st_csr_multi_round(void* csr, void* multi, const void* d_s_prev,
+                       void* d_s_next, const void* d_v_prev, void* d_v_cur,
+                       void* d_scratch, double eps, unsigned int k,
+                       unsigned int max_itr, unsigned int semantics,
+                       st_state* d_states, uint32_t* d_finished, void* stream);
 
 /* The batched sparse scheme, step by step (what st_solve_csr_batched runs);
  * `h` is a st_csr_batch_create handle, all vectors device [N] stacked,
