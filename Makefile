@@ -10,7 +10,8 @@ SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hi
             eigen_value_amd/csrc/st_multi.hip eigen_value_amd/csrc/st_rendezvous.hip \
             eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip \
             eigen_value_amd/csrc/st_csr_batch.hip eigen_value_amd/csrc/st_csr_transpose.hip \
-            eigen_value_amd/csrc/st_csr_terms.hip eigen_value_amd/csrc/st_csr_multi.hip
+            eigen_value_amd/csrc/st_csr_terms.hip eigen_value_amd/csrc/st_csr_multi.hip \
+            eigen_value_amd/csrc/st_csr_product.hip
 OBJ     := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
@@ -23,7 +24,8 @@ HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/c
             eigen_value_amd/csrc/st_half.h eigen_value_amd/csrc/st_csr.h \
             eigen_value_amd/csrc/st_csr_host.h eigen_value_amd/csrc/st_csr_batch.h \
             eigen_value_amd/csrc/st_csr_plan.h eigen_value_amd/csrc/st_csr_transpose.h \
-            eigen_value_amd/csrc/st_csr_terms.h eigen_value_amd/csrc/st_csr_multi.h
+            eigen_value_amd/csrc/st_csr_terms.h eigen_value_amd/csrc/st_csr_multi.h \
+            eigen_value_amd/csrc/st_csr_product.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 
@@ -83,8 +85,20 @@ csr_multi_sanitize: $(LIB) tests/cpp/csr_multi_sanitize.cpp eigen_value_amd/csrc
 	./build/csr_multi_sanitize build/csr_tables/table0.bin build/csr_tables/table1.bin \
 	  build/csr_tables/table2.bin
 
+# the host side of the product operator B A (st_csr_host.h: the validation of
+# two triples and of the rows of the product) under the host sanitizers, as
+# csr_terms_sanitize
+csr_product_sanitize: $(LIB) tests/cpp/csr_product_sanitize.cpp eigen_value_amd/csrc/st_csr_host.h
+	@mkdir -p build/csr_tables
+	$(PYTHON) tests/csr_cases.py build/csr_tables
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	  -fno-omit-frame-pointer -Ieigen_value_amd/csrc tests/cpp/csr_product_sanitize.cpp \
+	  -o build/csr_product_sanitize
+	./build/csr_product_sanitize build/csr_tables/table0.bin build/csr_tables/table1.bin \
+	  build/csr_tables/table2.bin
+
 clean:
 	rm -rf build eigen_value_amd/lib
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean probe csr_terms_sanitize csr_multi_sanitize
+.PHONY: all oracle clean probe csr_terms_sanitize csr_multi_sanitize csr_product_sanitize

@@ -381,6 +381,25 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_csr_multi_rowsum.restype = i32
     L.st_csr_multi_round.argtypes = [P, P, P, P, P, P, P, f64, u32, u32, u32, P, P, P]
     L.st_csr_multi_round.restype = i32
+    # the product operator B A (section 3g)
+    L.st_solve_csr_product.argtypes = [P, P, P, P, P, P, P, P, P]
+    L.st_solve_csr_product.restype = i64
+    L.st_csr_apply.argtypes = [P, P, P, P]
+    L.st_csr_apply.restype = i32
+    L.st_csr_product_scratch_bytes.argtypes = [u32]
+    L.st_csr_product_scratch_bytes.restype = u64
+    L.st_csr_product_shape_desc.argtypes = []
+    L.st_csr_product_shape_desc.restype = ctypes.c_char_p
+    L.st_csr_product_rowsum.argtypes = [P, P, P, P, P]
+    L.st_csr_product_rowsum.restype = i32
+    L.st_csr_product_round.argtypes = [P, P, P, P, P, P, P, f64, u32, u32, u32, P, P]
+    L.st_csr_product_round.restype = i32
+    L.max_eigen_value_csr_product_ex.argtypes = [P, i32, u32, u64, P, P, P, u64, P, P, P, u32,
+                                                 P, P, P, P, P]
+    L.max_eigen_value_csr_product_ex.restype = i64
+    L.max_eigen_value_csr_gram_ex.argtypes = [P, i32, u32, u64, P, P, P, i32, u32,
+                                              P, P, P, P, P]
+    L.max_eigen_value_csr_gram_ex.restype = i64
     L.st_csr_batch_create.argtypes = [P, i32, u32, P, u64, P, P, P,
                                       ctypes.POINTER(ctypes.c_void_p)]
     L.st_csr_batch_create.restype = i32
@@ -534,6 +553,33 @@ def check_terms_arg(u, w, n: int):
             if shape != (n,):
                 raise ValueError(f"terms: {name}_{j} has shape {shape}, ({n},) required")
     return ku
+
+
+ST_GRAM_ATA = 0
+ST_GRAM_AAT = 1
+CSR_PRODUCT_SYMBOLS = (
+    "st_solve_csr_product", "st_csr_apply", "st_csr_product_rowsum", "st_csr_product_round",
+    "st_csr_product_scratch_bytes", "st_csr_product_shape_desc",
+    "max_eigen_value_csr_product_ex", "max_eigen_value_csr_gram_ex")
+
+
+def csr_product_shape(L: Optional[ctypes.CDLL] = None) -> dict:
+    """st_csr_product_shape_desc as a dict (integers where they are)."""
+    L = L or load()
+    out = {}
+    for item in L.st_csr_product_shape_desc().decode().split():
+        k, v = item.split("=")
+        out[k] = int(v) if v.isdigit() else v
+    return out
+
+
+def gram_side(side) -> int:
+    """The ``side`` keyword of the Gram fronts as the C-ABI's code: ``"ata"``
+    (AᵀA) -> ST_GRAM_ATA, ``"aat"`` (AAᵀ) -> ST_GRAM_AAT.  Anything else is a
+    ValueError, raised before any library call."""
+    if isinstance(side, str) and side in ("ata", "aat"):
+        return ST_GRAM_ATA if side == "ata" else ST_GRAM_AAT
+    raise ValueError(f'side must be "ata" or "aat", got {side!r}')
 
 
 ST_CSR_MULTI_MAX = 8

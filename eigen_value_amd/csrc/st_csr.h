@@ -117,11 +117,49 @@ csr_lanes_sum(T x)
 // the sweep - e == end from the start - and its tot starts the fmas at 0.
 // KM >= K is the number of terms the instantiation holds registers for (the
 // u_j[r] live through the sweep: R * KM of them); it changes no result.
+// CsrPlain / CsrDivisor<T> (st_csr_product.h: the operator B A, two row
+// products per round).  CsrPlain: CsrOne's sweep and tree, then s_next[r] =
+// tot - no division, no v, nothing asked for but the row's entries and the
+// gathers (an empty row writes exactly 0).  CsrDivisor<T>: CsrOne, except
+// that the divisor is xdiv[r] and not the gathered vector's own element.
+// csr_mode<G> says which; every other policy is neither.
 struct CsrOne
 {
   static constexpr bool kStack = false;
   static constexpr bool kTerms = false;
   static constexpr int kK = 0;
+};
+struct CsrPlain
+{
+  static constexpr bool kStack = false;
+  static constexpr bool kTerms = false;
+  static constexpr int kK = 0;
+};
+template <typename T>
+struct CsrDivisor
+{
+  static constexpr bool kStack = false;
+  static constexpr bool kTerms = false;
+  static constexpr int kK = 0;
+  const T* xdiv; // [n] the divisor of each row
+};
+template <typename G>
+struct csr_mode
+{
+  static constexpr bool kPlain = false;
+  static constexpr bool kDivisor = false;
+};
+template <>
+struct csr_mode<CsrPlain>
+{
+  static constexpr bool kPlain = true;
+  static constexpr bool kDivisor = false;
+};
+template <typename T>
+struct csr_mode<CsrDivisor<T>>
+{
+  static constexpr bool kPlain = false;
+  static constexpr bool kDivisor = true;
 };
 constexpr int kCsrTermsMax = (int)csr::kTermsMax;
 template <typename T, int KM = kCsrTermsMax>
@@ -187,10 +225,14 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
   }
   // what the row's last step needs, asked for before the sweep
   T xr[R], sp[R], vp[R];
-  if constexpr (!ONES) {
+  constexpr bool kSumOnly = ONES || csr_mode<G>::kPlain; // s_next = tot
+  if constexpr (!kSumOnly) {
 #pragma unroll
     for (int j = 0; j < R; j++) {
-      xr[j] = x[r[j]];
+      if constexpr (csr_mode<G>::kDivisor)
+        xr[j] = g.xdiv[r[j]];
+      else
+        xr[j] = x[r[j]];
       sp[j] = s_prev[r[j]];
       vp[j] = v_prev[r[j]];
     }
@@ -259,7 +301,7 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
           tot = (uint32_t)q < g.K ? __builtin_fma(ut[j][q], dq[q], tot) : tot;
       }
       if (live[j] && t == L - 1) {
-        if constexpr (ONES) {
+        if constexpr (kSumOnly) {
           s_next[r[j]] = tot;
         } else {
           s_next[r[j]] = tot / xr[j];
@@ -285,7 +327,7 @@ csr_rows(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
         tot = (uint32_t)q < g.K ? __builtin_fma(ut[0][q], dq[q], tot) : tot;
     }
     if (live[0] && threadIdx.x == 0) {
-      if constexpr (ONES) {
+      if constexpr (kSumOnly) {
         s_next[r[0]] = tot;
       } else {
         s_next[r[0]] = tot / xr[0];

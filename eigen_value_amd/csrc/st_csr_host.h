@@ -3,8 +3,9 @@
 // a host CSR matrix.  Plain C++ without any HIP, so that it also compiles
 // into a stand-alone program (tests/cpp/csr_sanitize.cpp and, for the empty
 // rows flag and the low-rank terms, tests/cpp/csr_terms_sanitize.cpp, for the
-// multi-column packing and validation tests/cpp/csr_multi_sanitize.cpp, run
-// under the host sanitizers).  Included by st_csr.hip; not a public header.
+// multi-column packing and validation tests/cpp/csr_multi_sanitize.cpp, for
+// the product operator tests/cpp/csr_product_sanitize.cpp, run under the host
+// sanitizers).  Included by st_csr.hip; not a public header.
 //
 // Every function returns 0 (or a count) on success and -1 on failure with
 // the reason written to msg[cap].
@@ -296,6 +297,110 @@ check_terms_rows(uint32_t n, const int64_t* row_ptr, const T* vals, uint32_t K,
       describe_term_row(r, (double)st, msg, cap);
       return -1;
     }
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// The product operator M = B A (st_csr_product.hip), both factors n x n of one
+// dtype; no entry of M is formed.  Every row of M needs a positive entry.  The
+// device judges the s_0 its own K0 computes (finite and > 0); the host twin
+// below asks whether row r of B has an entry b > 0 whose column is a row of A
+// holding a value > 0.  For finite nonnegative factors the two predicates can
+// differ only where a product or a sum under- or overflows: b * (row sum of
+// A) may round to 0 or to inf on the device where the host sees a positive
+// entry.  Both print through describe_product_row.
+// ---------------------------------------------------------------------------
+inline void
+describe_product_row(uint32_t r, char* msg, size_t cap)
+{
+  snprintf(msg, cap,
+           "csr product: row %u of B·A has no positive entry: it would be "
+           "divided by zero", r);
+}
+
+// "csr: <text>" -> "csr product: factor B: <text>"
+inline void
+put_factor(const char* which, char* msg, size_t cap)
+{
+  char tmp[384];
+  snprintf(tmp, sizeof(tmp), "%s", msg);
+  const char* head = "csr: ";
+  size_t skip = 0;
+  while (head[skip] && tmp[skip] == head[skip])
+    skip++;
+  if (head[skip])
+    skip = 0;
+  snprintf(msg, cap, "csr product: factor %s: %s", which, tmp + skip);
+}
+
+// the rows of B A in ascending order; call only after both triples passed
+// check_host.  a_pos [n] is scratch of the caller: a_pos[c] = row c of A
+// holds a value > 0
+template <typename T>
+inline int
+check_product_rows(uint32_t n, const int64_t* b_row_ptr, const int32_t* b_col_idx,
+                   const T* b_vals, const int64_t* a_row_ptr, const T* a_vals,
+                   unsigned char* a_pos, char* msg, size_t cap)
+{
+  for (uint32_t c = 0; c < n; c++) {
+    a_pos[c] = 0;
+    for (int64_t e = a_row_ptr[c]; e < a_row_ptr[c + 1]; e++)
+      if (a_vals[e] > (T)0) {
+        a_pos[c] = 1;
+        break;
+      }
+  }
+  for (uint32_t r = 0; r < n; r++) {
+    bool any = false;
+    for (int64_t e = b_row_ptr[r]; e < b_row_ptr[r + 1] && !any; e++)
+      any = b_vals[e] > (T)0 && a_pos[(uint32_t)b_col_idx[e]] != 0;
+    if (!any) {
+      describe_product_row(r, msg, cap);
+      return -1;
+    }
+  }
+  return 0;
+}
+
+// a whole host product, in its fixed order: dtype and n (shared), B's triple
+// (no empty row: it would be an empty row of M), A's triple (empty rows legal
+// under a_flags & kEmptyRowsOk), then the rows of B A
+inline int
+check_product_host(int dtype, uint32_t n, uint64_t b_nnz, const int64_t* b_row_ptr,
+                   const int32_t* b_col_idx, const void* b_vals, uint64_t a_nnz,
+                   const int64_t* a_row_ptr, const int32_t* a_col_idx,
+                   const void* a_vals, uint32_t a_flags, unsigned char* a_pos,
+                   char* msg, size_t cap)
+{
+  if (check_host(dtype, n, b_nnz, b_row_ptr, b_col_idx, b_vals, msg, cap)) {
+    put_factor("B", msg, cap);
+    return -1;
+  }
+  if (check_host(dtype, n, a_nnz, a_row_ptr, a_col_idx, a_vals, msg, cap,
+                 (a_flags & kEmptyRowsOk) != 0)) {
+    put_factor("A", msg, cap);
+    return -1;
+  }
+  if (!a_pos) {
+    snprintf(msg, cap, "csr product: null scratch");
+    return -1;
+  }
+  return dtype ? check_product_rows<double>(
+                   n, b_row_ptr, b_col_idx, static_cast<const double*>(b_vals),
+                   a_row_ptr, static_cast<const double*>(a_vals), a_pos, msg, cap)
+               : check_product_rows<float>(
+                   n, b_row_ptr, b_col_idx, static_cast<const float*>(b_vals),
+                   a_row_ptr, static_cast<const float*>(a_vals), a_pos, msg, cap);
+}
+
+// the Gram operators of one matrix: side 0 = A^T A ("ata"), 1 = A A^T ("aat")
+inline int
+check_gram_side(int side, char* msg, size_t cap)
+{
+  if (side != 0 && side != 1) {
+    snprintf(msg, cap, "csr gram: side must be 0 (A^T A) or 1 (A A^T), got %d", side);
+    return -1;
   }
   return 0;
 }

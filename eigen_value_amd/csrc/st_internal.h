@@ -196,6 +196,24 @@ int launch_csr_terms_round(const CsrHandle* h, const CsrTermsHandle* t,
                            void* v_cur, void* x, void* dots_part, double eps,
                            uint32_t k, uint32_t max_itr, uint32_t semantics,
                            st_state* st, hipStream_t stream);
+// the product operator B A of two matrix handles (st_csr_product.hip), never
+// formed.  -1 + error unless b and a agree in n, dtype and device (in that
+// order)
+int csr_product_check_pair(const CsrHandle* b, const CsrHandle* a, const char* what);
+// bytes of one of the round's two scratch vectors (x, then y), 256-byte aligned
+size_t csr_product_vec_bytes(uint32_t n);
+// y = H x in the row order of the solve; no division, an empty row gives 0
+int launch_csr_apply(const CsrHandle* h, const void* x, void* y, hipStream_t stream);
+// K0: y = the row sums of A, s = B y
+int launch_csr_product_rowsum(const CsrHandle* b, const CsrHandle* a, void* s, void* y,
+                              hipStream_t stream);
+int launch_csr_product_round(const CsrHandle* b, const CsrHandle* a, const void* s_prev,
+                             void* s_next, const void* v_prev, void* v_cur, void* x,
+                             void* y, double eps, uint32_t k, uint32_t max_itr,
+                             uint32_t semantics, st_state* st, hipStream_t stream);
+// d_err[0] (preset to ~0) <- the lowest row whose s0 is not finite and > 0
+int launch_csr_product_check_s0(int dtype, const void* s0, uint32_t n,
+                                unsigned long long* d_err, hipStream_t stream);
 // up to 8 operators A + sum_j u_{c,j} w_{c,j}^T on one matrix handle
 // (st_csr_multi.hip): the validated term vectors packed [K][n][CP], and the
 // packed vectors of the solve loop.  Everything is the object's own (one

@@ -319,13 +319,16 @@ resolve(const st_options* opt, Resolved* r)
 // the same matrix-free loop with st_csr.hip's K0 and two-launch round, x in
 // the first (here unused) slot of the deferred ring; with `terms` the
 // operator is A + sum_j u_j w_j^T (st_csr_terms.hip's K0 and three-launch
-// round, dots and partials in the flat scratch, unused here)
+// round, dots and partials in the flat scratch, unused here); with `csr_b`
+// the operator is the product csr_b * csr (st_csr_product.hip's K0 and
+// three-launch round, y in the second slot of the ring)
 template <typename T>
 int64_t
 solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
              T* eigen_val, uint32_t* iter_cnt, const st_options* opt,
              st_stats* stats, bool flush_matrix = true, int storage = 0,
-             const CsrHandle* csr = nullptr, const CsrTermsHandle* terms = nullptr)
+             const CsrHandle* csr = nullptr, const CsrTermsHandle* terms = nullptr,
+             const CsrHandle* csr_b = nullptr)
 {
   static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value,
                 "fp32 / fp64 vectors");
@@ -382,6 +385,8 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   if (terms && ensure_part(c, csr_terms_dots_bytes(terms->K)))
     return -1;
   T* d_part = reinterpret_cast<T*>(c->d_part);
+  // the product round's y: the ring's second slot (x is its first)
+  T* const d_y = reinterpret_cast<T*>((char*)c->d_vec + 5 * c->vec_bytes);
   // rounds per host flag check: the launches queued behind the stopping
   // round still run as gated no-ops, and a gated flat round is two launches
   // of up to millions of workgroups (~10 us each), so the flat form checks
@@ -424,8 +429,9 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   }
   T* const s0 = defer ? ring_s[0] : s_buf[0];
   if (csr) { // K0 on the CSR matrix
-    if (terms ? launch_csr_terms_rowsum(csr, terms, s0, d_part, s)
-              : launch_csr_rowsum(csr, s0, s))
+    if (csr_b    ? launch_csr_product_rowsum(csr_b, csr, s0, d_y, s)
+        : terms ? launch_csr_terms_rowsum(csr, terms, s0, d_part, s)
+                : launch_csr_rowsum(csr, s0, s))
       return -1;
   } else if (storage != 0) { // K0 on the 16-bit matrix
     if constexpr (std::is_same<T, float>::value) {
@@ -465,7 +471,12 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
         ev.push_back(eb);
         (void)hipEventRecord(ea, s);
       }
-      if (csr && terms) // launch k+1 evaluates round k
+      if (csr && csr_b) // launch k+1 evaluates round k
+        rc |= launch_csr_product_round(csr_b, csr, s_buf[cur], s_buf[cur ^ 1],
+                                       vb[k & 1], vb[(k + 1) & 1], ring_s[0],
+                                       d_y, o.eps, k + 1, o.max_itr,
+                                       o.semantics, c->d_state, s);
+      else if (csr && terms)
         rc |= launch_csr_terms_round(csr, terms, s_buf[cur], s_buf[cur ^ 1],
                                      vb[k & 1], vb[(k + 1) & 1], ring_s[0], d_part,
                                      o.eps, k + 1, o.max_itr, o.semantics,
@@ -907,6 +918,252 @@ solve_host_csr_left(Context* c, int dtype, uint32_t n, uint64_t nnz,
   const int64_t rc =
     solve_csr(c, ht, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local);
   (void)csr_destroy(ht);
+  if (rc < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  const double us = tr_ms * 1000.0;
+  local.transpose_us = us < 4294967295.0 ? (uint32_t)us : 0xffffffffu;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + tr_ms + local.loop_ms);
+}
+
+// The solve on the product operator B A of two validated handles (never
+// formed): solve_csr's loop with st_csr_product.hip's launchers.  Checked
+// before any round, in this order: the flags, the pair (n, dtype, device), the
+// queue's device, then s_0 of the operator on the device - every row finite
+// and > 0, the lowest offender named (a row of M with a positive entry stays
+// positive for every positive x, so no round divides by zero).
+int64_t
+solve_csr_product(Context* c, const CsrHandle* b, const CsrHandle* a, void* d_v_out,
+                  void* v_host, void* eigen_val, uint32_t* iter_cnt,
+                  const st_options* opt, st_stats* stats)
+{
+  if (csr_product_check_pair(b, a, "st_solve_csr_product"))
+    return -1;
+  if (csr_check_flags(opt))
+    return -1;
+  ST_REQUIRE(c, "null queue");
+  ST_REQUIRE(c->device == a->device,
+             "csr product solve: the matrices live on device %d, the queue on %d",
+             a->device, c->device);
+  ST_REQUIRE(eigen_val && iter_cnt, "null output pointer");
+  ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
+  const size_t elem = a->dtype ? 8 : 4;
+  if (ensure_device(c) || ensure_vectors(c, elem * (size_t)a->n) || ensure_part(c, 256))
+    return -1;
+  {
+    // s_0 into the loop's own first buffer, y in the ring's second slot; the
+    // solve computes both again
+    void* s0 = c->d_vec;
+    void* y = (char*)c->d_vec + 5 * c->vec_bytes;
+    unsigned long long* d_err = static_cast<unsigned long long*>(c->d_part);
+    unsigned long long err = 0;
+    ST_CHECK(hipMemsetAsync(d_err, 0xff, sizeof(err), c->stream));
+    if (launch_csr_product_rowsum(b, a, s0, y, c->stream) ||
+        launch_csr_product_check_s0(a->dtype, s0, a->n, d_err, c->stream))
+      return -1;
+    ST_CHECK(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
+    ST_CHECK(hipStreamSynchronize(c->stream));
+    if (err != ~0ull) {
+      char msg[384];
+      csr::describe_product_row((uint32_t)err, msg, sizeof(msg));
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  // never dereferenced: solve_device reads the matrices through the handles
+  void* tag = const_cast<CsrHandle*>(a);
+  if (a->dtype)
+    return solve_device<double>(c, static_cast<double*>(tag), a->n,
+                                static_cast<double*>(d_v_out),
+                                static_cast<double*>(v_host),
+                                static_cast<double*>(eigen_val), iter_cnt, opt,
+                                stats, false, 0, a, nullptr, b);
+  return solve_device<float>(c, static_cast<float*>(tag), a->n,
+                             static_cast<float*>(d_v_out), static_cast<float*>(v_host),
+                             static_cast<float*>(eigen_val), iter_cnt, opt, stats,
+                             false, 0, a, nullptr, b);
+}
+
+// one host triple into the workspace at `base`: [row_ptr | vals | col_idx],
+// each at a 256-byte aligned offset
+struct CsrSlots
+{
+  size_t b_ptr, b_val, b_col;
+  size_t bytes() const { return b_ptr + b_val + b_col; }
+  int64_t* ptr(char* base) const { return reinterpret_cast<int64_t*>(base); }
+  void* val(char* base) const { return base + b_ptr; }
+  int32_t* col(char* base) const { return reinterpret_cast<int32_t*>(base + b_ptr + b_val); }
+};
+
+CsrSlots
+csr_slots(int dtype, uint32_t n, uint64_t nnz)
+{
+  const size_t elem = dtype ? 8 : 4;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  return CsrSlots{ up(8 * ((size_t)n + 1)), up(elem * nnz), up(4 * nnz) };
+}
+
+int
+csr_copy_in(Context* c, const CsrSlots& sl, char* base, int dtype, uint32_t n,
+            uint64_t nnz, const int64_t* row_ptr, const int32_t* col_idx,
+            const void* vals)
+{
+  const size_t elem = dtype ? 8 : 4;
+  ST_CHECK(hipMemcpyAsync(sl.ptr(base), row_ptr, 8 * ((size_t)n + 1),
+                          hipMemcpyHostToDevice, c->stream));
+  ST_CHECK(hipMemcpyAsync(sl.val(base), vals, elem * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipMemcpyAsync(sl.col(base), col_idx, 4 * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  return 0;
+}
+
+// The host-pointer solve of B A: everything validated on the host first
+// (dtype, opt's flags, `flags`, B's triple, A's triple, the rows of B A); the
+// workspace holds B's three arrays, then A's
+int64_t
+solve_host_csr_product(Context* c, int dtype, uint32_t n, uint64_t b_nnz,
+                       const int64_t* b_row_ptr, const int32_t* b_col_idx,
+                       const void* b_vals, uint64_t a_nnz, const int64_t* a_row_ptr,
+                       const int32_t* a_col_idx, const void* a_vals, uint32_t flags,
+                       void* eigen_val, void* eigen_vec, uint32_t* iter_cnt,
+                       const st_options* opt, st_stats* stats)
+{
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  if (csr_check_flags(opt))
+    return -1;
+  ST_REQUIRE((flags & ~csr::kEmptyRowsOk) == 0,
+             "max_eigen_value_csr_product_ex: unknown flags %u", flags);
+  {
+    char msg[384];
+    std::vector<unsigned char> a_pos(n && n < 0x80000000u ? n : 1);
+    if (csr::check_product_host(dtype, n, b_nnz, b_row_ptr, b_col_idx, b_vals, a_nnz,
+                                a_row_ptr, a_col_idx, a_vals, flags, a_pos.data(), msg,
+                                sizeof(msg))) {
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  ST_REQUIRE(eigen_val && eigen_vec && iter_cnt, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  const CsrSlots sb = csr_slots(dtype, n, b_nnz), sa = csr_slots(dtype, n, a_nnz);
+  if (ensure_matrix(c, sb.bytes() + sa.bytes()))
+    return -1;
+  char* base_b = static_cast<char*>(c->d_mat);
+  char* base_a = base_b + sb.bytes();
+  const auto t0 = std::chrono::steady_clock::now();
+  if (csr_copy_in(c, sb, base_b, dtype, n, b_nnz, b_row_ptr, b_col_idx, b_vals) ||
+      csr_copy_in(c, sa, base_a, dtype, n, a_nnz, a_row_ptr, a_col_idx, a_vals))
+    return -1;
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  CsrHandle* hb = nullptr;
+  if (csr_create(dtype, n, b_nnz, sb.ptr(base_b), sb.col(base_b), sb.val(base_b),
+                 c->stream, &hb))
+    return -1;
+  CsrHandle* ha = nullptr;
+  if (csr_create(dtype, n, a_nnz, sa.ptr(base_a), sa.col(base_a), sa.val(base_a),
+                 c->stream, &ha, flags)) {
+    (void)csr_destroy(hb);
+    return -1;
+  }
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  const int64_t rc = solve_csr_product(c, hb, ha, nullptr, eigen_vec, eigen_val,
+                                       iter_cnt, opt, &local);
+  (void)csr_destroy(ha);
+  (void)csr_destroy(hb);
+  if (rc < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
+}
+
+// The Gram operators of ONE host matrix: side 0 = A^T A, 1 = A A^T.  Validated
+// on the host (nnz < 2^32, the side, dtype, flags, the triple, then the product
+// on a host transposition), A copied in and transposed on the device
+// (st_csr_transpose_ex, empty rows and columns legal there: what the product
+// cannot take the host check has refused)
+int64_t
+solve_host_csr_gram(Context* c, int dtype, uint32_t n, uint64_t nnz,
+                    const int64_t* row_ptr, const int32_t* col_idx, const void* vals,
+                    int side, uint32_t flags, void* eigen_val, void* eigen_vec,
+                    uint32_t* iter_cnt, const st_options* opt, st_stats* stats)
+{
+  char msg[384];
+  if (csr::check_transpose_nnz(nnz, msg, sizeof(msg)) ||
+      csr::check_gram_side(side, msg, sizeof(msg))) {
+    set_error("%s", msg);
+    return -1;
+  }
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  if (csr_check_flags(opt))
+    return -1;
+  ST_REQUIRE((flags & ~csr::kEmptyRowsOk) == 0,
+             "max_eigen_value_csr_gram_ex: unknown flags %u", flags);
+  if (csr_check_host(dtype, n, nnz, row_ptr, col_idx, vals, flags))
+    return -1;
+  {
+    const size_t elem = dtype ? 8 : 4;
+    std::vector<int64_t> t_ptr((size_t)n + 1);
+    std::vector<int32_t> t_col(nnz);
+    std::vector<unsigned char> t_val(elem * nnz), a_pos(n);
+    if (csr::transpose_host(dtype, n, nnz, row_ptr, col_idx, vals, t_ptr.data(),
+                            t_col.data(), t_val.data(), msg, sizeof(msg),
+                            csr::kEmptyRowsOk) ||
+        (side == 0 ? csr::check_product_host(dtype, n, nnz, t_ptr.data(), t_col.data(),
+                                             t_val.data(), nnz, row_ptr, col_idx, vals,
+                                             csr::kEmptyRowsOk, a_pos.data(), msg,
+                                             sizeof(msg))
+                   : csr::check_product_host(dtype, n, nnz, row_ptr, col_idx, vals, nnz,
+                                             t_ptr.data(), t_col.data(), t_val.data(),
+                                             csr::kEmptyRowsOk, a_pos.data(), msg,
+                                             sizeof(msg)))) {
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  ST_REQUIRE(eigen_val && eigen_vec && iter_cnt, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  const CsrSlots sl = csr_slots(dtype, n, nnz);
+  if (ensure_matrix(c, 2 * sl.bytes()))
+    return -1;
+  char* base = static_cast<char*>(c->d_mat);
+  char* base_t = base + sl.bytes();
+  const auto t0 = std::chrono::steady_clock::now();
+  if (csr_copy_in(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals))
+    return -1;
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  CsrHandle* h = nullptr;
+  if (csr_create(dtype, n, nnz, sl.ptr(base), sl.col(base), sl.val(base), c->stream, &h,
+                 csr::kEmptyRowsOk))
+    return -1;
+  const double h2d = ms_since(t0);
+  const auto t1 = std::chrono::steady_clock::now();
+  CsrHandle* ht = nullptr;
+  if (csr_transpose(h, sl.ptr(base_t), sl.col(base_t), sl.val(base_t), c->stream, &ht,
+                    csr::kEmptyRowsOk)) {
+    (void)csr_destroy(h);
+    return -1;
+  }
+  const double tr_ms = ms_since(t1);
+  st_stats local{};
+  const int64_t rc =
+    side == 0 ? solve_csr_product(c, ht, h, nullptr, eigen_vec, eigen_val, iter_cnt, opt,
+                                  &local)
+              : solve_csr_product(c, h, ht, nullptr, eigen_vec, eigen_val, iter_cnt, opt,
+                                  &local);
+  (void)csr_destroy(ht);
+  (void)csr_destroy(h);
   if (rc < 0)
     return -1;
   local.h2d_ms = h2d;
@@ -2357,6 +2614,54 @@ max_eigen_value_csr_left_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
   st::DeviceGuard guard;
   return st::solve_host_csr_left(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
                                  vals, eigen_val, eigen_vec, iter_cnt, opt, stats);
+}
+
+int64_t
+st_solve_csr_product(void* wq, void* csr_b, void* csr_a, void* d_eigen_vec,
+                     void* eigen_vec_host, void* eigen_val, unsigned int* iter_cnt,
+                     const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  const st::CsrHandle* b = st::as_csr(csr_b, "st_solve_csr_product (B)");
+  if (!b)
+    return -1;
+  const st::CsrHandle* a = st::as_csr(csr_a, "st_solve_csr_product (A)");
+  if (!a)
+    return -1;
+  return st::solve_csr_product(st::as_ctx(wq), b, a, d_eigen_vec, eigen_vec_host,
+                               eigen_val, iter_cnt, opt, stats);
+}
+
+int64_t
+max_eigen_value_csr_product_ex(void* wq, int dtype, uint32_t n, uint64_t b_nnz,
+                               const int64_t* b_row_ptr, const int32_t* b_col_idx,
+                               const void* b_vals, uint64_t a_nnz,
+                               const int64_t* a_row_ptr, const int32_t* a_col_idx,
+                               const void* a_vals, unsigned int flags, void* eigen_val,
+                               void* eigen_vec, unsigned int* iter_cnt,
+                               const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_csr_product(st::as_ctx(wq), dtype, n, b_nnz, b_row_ptr,
+                                    b_col_idx, b_vals, a_nnz, a_row_ptr, a_col_idx,
+                                    a_vals, flags, eigen_val, eigen_vec, iter_cnt, opt,
+                                    stats);
+}
+
+int64_t
+max_eigen_value_csr_gram_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                            const int64_t* row_ptr, const int32_t* col_idx,
+                            const void* vals, int side, unsigned int flags,
+                            void* eigen_val, void* eigen_vec, unsigned int* iter_cnt,
+                            const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_csr_gram(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx, vals,
+                                 side, flags, eigen_val, eigen_vec, iter_cnt, opt,
+                                 stats);
 }
 
 int

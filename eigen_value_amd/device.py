@@ -8,6 +8,7 @@ a missing library raises, a non-CUDA tensor raises.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 from . import _lib
@@ -677,6 +678,91 @@ def csr_mfree_round(csr: CsrMatrix, s_prev, s_next, v_prev, v_cur, x, state, *,
         k, max_itr, semantics, _ptr(state), _stream(csr.device)), "csr_mfree_round")
 
 
+def _check_csr(csr, name: str = "csr") -> None:
+    if not isinstance(csr, CsrMatrix):
+        raise TypeError(f"{name}: a CsrMatrix required, got {type(csr).__name__}")
+    if not csr.handle.value:
+        raise ValueError(f"{name}: the matrix is closed")
+
+
+def _check_product_pair(B, A) -> None:
+    """What every Python front checks of the factors of ``B·A`` before any
+    library call, in the library's order: both alive, same n, dtype, device."""
+    _check_csr(B, "B")
+    _check_csr(A, "A")
+    if B.n != A.n:
+        raise ValueError(f"product: the factors differ in n (B: {B.n}, A: {A.n})")
+    if B.dtype != A.dtype:
+        raise TypeError(f"product: the factors differ in dtype (B: {B.dtype}, A: {A.dtype})")
+    if B.device != A.device:
+        raise ValueError(f"product: the factors live on different devices (B: {B.device}, "
+                         f"A: {A.device})")
+
+
+def csr_apply(csr: CsrMatrix, x, out=None):
+    """``y = A x`` (``st_csr_apply``): the plain CSR row product in the solve's
+    fixed summation order - a reproducible SpMV.  No division; an empty row
+    gives exactly 0.  ``x`` [n] of the matrix's dtype and device; ``out`` must
+    not be ``x``."""
+    torch = _torch()
+    _check_csr(csr)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"x must be a torch tensor, got {type(x).__name__}")
+    if x.dtype != csr.dtype:
+        raise TypeError(f"x is {x.dtype}, the matrix {csr.dtype}")
+    if tuple(x.shape) != (csr.n,):
+        raise ValueError(f"x has shape {tuple(x.shape)}, ({csr.n},) required")
+    if x.device != csr.device:
+        raise ValueError(f"x on {x.device}, the matrix on {csr.device}")
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty(csr.n, dtype=csr.dtype, device=csr.device)
+    _check_cuda(out)
+    assert out.dtype == csr.dtype and out.numel() >= csr.n and out.is_contiguous()
+    _lib.check(_lib.load().st_csr_apply(csr.handle, _ptr(x), _ptr(out), _stream(csr.device)),
+               "csr_apply")
+    return out
+
+
+def csr_product_scratch(A: CsrMatrix):
+    """A fresh scratch tensor for ``csr_product_rowsum`` / ``csr_product_round``
+    (``st_csr_product_scratch_bytes``): x in its first half, y in its second."""
+    torch = _torch()
+    nbytes = int(_lib.load().st_csr_product_scratch_bytes(A.n))
+    return torch.zeros(nbytes, dtype=torch.uint8, device=A.device)
+
+
+def csr_product_rowsum(B: CsrMatrix, A: CsrMatrix, scratch, out=None):
+    """s_0 of ``B·A`` (``st_csr_product_rowsum``): launch 0 - the row sums of
+    ``A`` into the scratch's second half, then ``B`` applied to them."""
+    torch = _torch()
+    _check_product_pair(B, A)
+    if out is None:
+        out = torch.empty(A.n, dtype=A.dtype, device=A.device)
+    _check_cuda(out, scratch)
+    assert out.dtype == A.dtype and out.numel() >= A.n
+    _lib.check(_lib.load().st_csr_product_rowsum(B.handle, A.handle, _ptr(out), _ptr(scratch),
+                                                 _stream(A.device)), "csr_product_rowsum")
+    return out
+
+
+def csr_product_round(B: CsrMatrix, A: CsrMatrix, s_prev, s_next, v_prev, v_cur, scratch,
+                      state, *, eps: float = 1e-3, k: int = 1,
+                      max_itr: int = _lib.ST_MAX_ITR,
+                      semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Launch k >= 1 on ``B·A`` (``st_csr_product_round``): ``csr_mfree_round``'s
+    contract in three launches - x = v_prev * s_prev, y = A x, s_next = (B y) /
+    x; x and y stand in the two halves of ``scratch`` afterwards."""
+    _check_product_pair(B, A)
+    _check_cuda(s_prev, s_next, v_prev, v_cur, scratch, state)
+    assert all(t.dtype == A.dtype and t.numel() >= A.n and t.is_contiguous()
+               for t in (s_prev, s_next, v_prev, v_cur))
+    _lib.check(_lib.load().st_csr_product_round(
+        B.handle, A.handle, _ptr(s_prev), _ptr(s_next), _ptr(v_prev), _ptr(v_cur),
+        _ptr(scratch), float(eps), k, max_itr, semantics, _ptr(state), _stream(A.device)),
+        "csr_product_round")
+
+
 class CsrBatch:
     """Many nonnegative sparse matrices in STACKED CSR storage on the device,
     validated and planned (``st_csr_batch_create``): ``crow_indices`` int64
@@ -1248,6 +1334,82 @@ class DeviceSolver:
             terms.close()
             Pt.close()
         return v / v.sum(), lam, it, stats
+
+    def solve_csr_product(self, B: "CsrMatrix", A: "CsrMatrix", *,
+                          eps: Optional[float] = None, max_itr: int = 0,
+                          semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
+                          trace: bool = False, time_kernels: bool = False,
+                          left: bool = False):
+        """The matrix-free solve of the product operator ``B·A``
+        (``st_solve_csr_product``), which is never formed: two CSR row
+        products per round, both in ``solve_csr``'s summation order.  ``B``
+        and ``A`` share n, dtype and device; the same matrix twice gives
+        ``A²``.  ``A`` may have empty rows; every row of ``B·A`` needs a
+        positive entry (``EigenValueError`` naming the lowest row without
+        one).  Returns (λ, v, iterations, stats) as ``solve_csr``; with the
+        identity as one factor every bit is ``solve_csr``'s on the other.
+
+        ``left=True`` solves ``Aᵀ·Bᵀ`` - the left Perron vector of ``B·A`` -
+        from the cached transposes (``.T``, made on this solver's queue at
+        the first use and kept)."""
+        if not isinstance(left, bool):
+            raise TypeError(f"left must be a bool, got {type(left).__name__}")
+        torch = _torch()
+        _check_product_pair(B, A)
+        if A.device.index != (self.device.index if self.device.index is not None
+                              else torch.cuda.current_device()):
+            raise ValueError(f"matrices on {A.device}, solver context on {self.device}")
+        if left:
+            if A._t is None:               # the new left factor: no empty row, so
+                A._t = A.transpose(self)   # an empty column of A is refused by name
+            if B._t is None:               # the new right factor may have empty rows
+                B._t = B.transpose(self, allow_empty=True)
+            return self.solve_csr_product(A.T, B.T, eps=eps, max_itr=max_itr,
+                                          semantics=semantics, batch=batch, trace=trace,
+                                          time_kernels=time_kernels)
+        v = torch.empty(A.n, dtype=A.dtype, device=A.device)
+        ev = (ctypes.c_double if A.dtype_code else ctypes.c_float)()
+        it = ctypes.c_uint32()
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace else 0))
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
+        stats = _lib.st_stats()
+        self._trace = (A.n, A.dtype)
+        _lib.check(self.L.st_set_stream(self.q, _stream(A.device)), "st_set_stream")
+        rc = self.L.st_solve_csr_product(self.q, B.handle, A.handle, _ptr(v), None,
+                                         ctypes.byref(ev), ctypes.byref(it),
+                                         ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(rc, "st_solve_csr_product")
+        return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def hits(self, links: "CsrMatrix", **solve_options):
+        """HITS of a link graph, on the device throughout.  ``links`` is a
+        nonnegative link-weight ``CsrMatrix`` (row = source); nodes without
+        out-links (empty rows, ``allow_empty_rows=True``) are fine, a node
+        without in-links (an empty column) is refused by name, as
+        ``transpose()`` does.  Authorities are the Perron vector of
+        ``linksᵀ·links``, solved as a product (``solve_csr_product(links.T,
+        links)``, the transposition made on the device); hubs are ``links``
+        applied to them (``csr_apply``).  ``solve_options`` are
+        ``solve_csr_product``'s (eps, max_itr, semantics, batch, trace,
+        time_kernels).
+
+        Returns ``(authorities with sum 1, hubs with sum 1, σ, iterations,
+        stats)``; σ = √λ is the largest singular value of ``links``."""
+        _check_csr(links, "links")
+        if "left" in solve_options:
+            raise TypeError("hits builds its own transposition")
+        lt = links.transpose(self)
+        try:
+            lam, v, it, stats = self.solve_csr_product(lt, links, **solve_options)
+        finally:
+            lt.close()
+        authorities = v / v.sum()
+        h = csr_apply(links, authorities)
+        hubs = h / h.sum()
+        return authorities, hubs, math.sqrt(lam), it, stats
 
     def solve_csr_multi(self, csr: "CsrMatrix", mterms: "CsrMultiTerms", *,
                         eps: Optional[float] = None, max_itr: int = 0,

@@ -385,6 +385,104 @@ class EigenValue:
         _lib.check(ts, "max_eigen_value_csr_multi_ex", self.so_lib)
         return eigen_vals, eigen_vecs, int(ts), iter_cnts, converged
 
+    def _csr_host(self, m, name: str):
+        """One host matrix of a product front as checked contiguous arrays:
+        (indptr int64, indices int32, data float32 / float64, n)."""
+        indptr, indices, data, n = self._csr_triple(m)
+        data = np.ascontiguousarray(data)
+        if data.dtype not in (np.float32, np.float64):
+            raise TypeError(f"{name}: data must be float32 or float64, got {data.dtype}")
+        indices = np.asarray(indices)
+        if indices.dtype.kind not in "iu":
+            raise TypeError(f"{name}: indices must be an integer array, got {indices.dtype}")
+        if indices.size and (indices.min() < -2**31 or indices.max() >= 2**31):
+            raise _lib.EigenValueError(f"{name}: a column index does not fit int32")
+        if len(indices) != len(data):
+            raise ValueError(f"{name}: indices and data differ in length")
+        return (np.ascontiguousarray(indptr, dtype=np.int64),
+                np.ascontiguousarray(indices, dtype=np.int32), data, n)
+
+    def _product_options(self, n, dtype, eps, max_itr, semantics, batch, time_kernels,
+                         trace_sums):
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace_sums else 0))
+        self._trace = (n, dtype)
+        return _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                               batch, flags)
+
+    def similarity_transform_csr_product(self, B, A, *, eps: Optional[float] = None,
+                                         max_itr: int = 0,
+                                         semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
+                                         time_kernels: bool = False, trace_sums: bool = False,
+                                         allow_empty_rows: bool = False):
+        """The matrix-free solve of the PRODUCT ``B·A`` of two nonnegative
+        sparse matrices (``max_eigen_value_csr_product_ex``); the product is
+        never formed - two CSR row products per round.  ``B`` and ``A`` are
+        each an ``(indptr, indices, data)`` triple of numpy arrays, a
+        ``scipy.sparse`` matrix or a ``torch.sparse_csr`` tensor, square of
+        one size and one dtype (float32 or float64).  ``allow_empty_rows``
+        accepts rows of ``A`` without an entry.  Everything is validated on
+        the host - the two matrices, then every row of ``B·A`` for a positive
+        entry, the error naming the lowest row without one.
+
+        Returns ``(λ, v, ts_ms, iterations)`` in the dtype of the data."""
+        if not isinstance(allow_empty_rows, bool):
+            raise TypeError("allow_empty_rows must be a bool, got "
+                            f"{type(allow_empty_rows).__name__}")
+        bp, bi, bd, bn = self._csr_host(B, "B")
+        ap, ai, ad, an = self._csr_host(A, "A")
+        if bn != an:
+            raise ValueError(f"product: the factors differ in n (B: {bn}, A: {an})")
+        if bd.dtype != ad.dtype:
+            raise TypeError(f"product: the factors differ in dtype (B: {bd.dtype}, "
+                            f"A: {ad.dtype})")
+        n = an
+        opt = self._product_options(n, ad.dtype, eps, max_itr, semantics, batch, time_kernels,
+                                    trace_sums)
+        eigen_val = np.empty(1, dtype=ad.dtype)
+        eigen_vec = np.empty(n, dtype=ad.dtype)
+        iter_cnt = np.zeros(1, dtype=np.uint32)
+        dtype = _lib.DTYPE_F32 if ad.dtype == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_csr_product_ex(
+            self.sycl_q, dtype, n, len(bd), bp.ctypes.data, bi.ctypes.data, bd.ctypes.data,
+            len(ad), ap.ctypes.data, ai.ctypes.data, ad.ctypes.data,
+            _lib.ST_CSR_EMPTY_ROWS_OK if allow_empty_rows else 0,
+            eigen_val.ctypes.data, eigen_vec.ctypes.data, iter_cnt.ctypes.data,
+            ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_csr_product_ex", self.so_lib)
+        return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
+
+    def similarity_transform_csr_gram(self, A, side: str = "ata", *,
+                                      eps: Optional[float] = None, max_itr: int = 0,
+                                      semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
+                                      time_kernels: bool = False, trace_sums: bool = False,
+                                      allow_empty_rows: bool = False):
+        """The Gram operators of ONE sparse matrix
+        (``max_eigen_value_csr_gram_ex``): ``side="ata"`` solves ``AᵀA`` (λ is
+        the square of the spectral norm of ``A``, v the HITS authorities),
+        ``side="aat"`` solves ``AAᵀ`` (the hubs).  ``A`` as
+        ``similarity_transform_csr_product`` takes a factor; it is transposed
+        on the device.  Returns ``(λ, v, ts_ms, iterations)``."""
+        if not isinstance(allow_empty_rows, bool):
+            raise TypeError("allow_empty_rows must be a bool, got "
+                            f"{type(allow_empty_rows).__name__}")
+        code = _lib.gram_side(side)
+        ap, ai, ad, n = self._csr_host(A, "A")
+        opt = self._product_options(n, ad.dtype, eps, max_itr, semantics, batch, time_kernels,
+                                    trace_sums)
+        eigen_val = np.empty(1, dtype=ad.dtype)
+        eigen_vec = np.empty(n, dtype=ad.dtype)
+        iter_cnt = np.zeros(1, dtype=np.uint32)
+        dtype = _lib.DTYPE_F32 if ad.dtype == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_csr_gram_ex(
+            self.sycl_q, dtype, n, len(ad), ap.ctypes.data, ai.ctypes.data, ad.ctypes.data,
+            code, _lib.ST_CSR_EMPTY_ROWS_OK if allow_empty_rows else 0,
+            eigen_val.ctypes.data, eigen_vec.ctypes.data, iter_cnt.ctypes.data,
+            ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_csr_gram_ex", self.so_lib)
+        return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
+
     @staticmethod
     def _csr_triple(m):
         """(indptr, indices, data, n) of one matrix of a sparse batch."""

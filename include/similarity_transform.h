@@ -815,6 +815,91 @@ int64_t max_eigen_value_csr_multi_ex(void* wq, int dtype, uint32_t n,
                                      const st_options* opt, st_stats* stats);
 
 /* ---------------------------------------------------------------------- */
+/* 3g. sparse (CSR) solve on a product operator B A                        */
+/* ---------------------------------------------------------------------- */
+
+/* The operator M = B A: A and B two st_csr_create / st_csr_create_ex handles
+ * of the same n, dtype and device; the same handle twice gives A^2.  No entry
+ * of M is stored or formed (it would hold about d^2 entries per row where the
+ * factors hold 2 d): a round of st_solve_csr becomes
+ *   x      = v_prev * s_prev                      (k_csr_prep, unchanged)
+ *   y[r]   = row r of A times x                   (k_csrp_apply, A's plan)
+ *   tot_r  = row r of B times y                   (k_csrp_final, B's plan)
+ *   s_next = tot_r / x[r];  v_cur[r] = v_prev[r] * (s_prev[r] / m)
+ * and launch 0 is y = the row sums of A (st_csr_rowsum), s_0 = B y.  Both row
+ * products sum in st_solve_csr's order (section 3c), so a row's result
+ * depends only on its own entries and the gathered vector.  Three launches
+ * per round, all gated on the state as st_csr_mfree_round's two; stop test,
+ * m, lambda, counts, both semantics, batches, tracing, timing as
+ * st_solve_csr.  With the identity as one factor every bit is st_solve_csr's
+ * on the other.  No float atomics, no workgroup waits on another.
+ *
+ * With st_csr_transpose_ex this gives HITS (authorities: A^T A, hubs: A A^T),
+ * the spectral norm sqrt(lambda_max(A^T A)), SALSA, two-step chains P^2 and
+ * bipartite projections B B^T.
+ *
+ * Empty rows: A may have them (ST_CSR_EMPTY_ROWS_OK; such a row gives y[r] =
+ * exactly 0).  Every row of M needs a positive entry.  Checked before any
+ * round, in this order: both handles alive, same n, same dtype, same device,
+ * then launch 0 on the device - every s_0[r] finite and > 0, else "row r of
+ * B·A has no positive entry" with the lowest r (a row of M with a positive
+ * entry stays positive for every positive x, so no round divides by zero).
+ * An empty row of B is such a row.
+ *
+ * Not offered: rectangular factors (pad to square with empty rows and
+ * columns), more than two factors, terms on a product, batched or
+ * multi-column products, mixed dtypes. */
+int64_t st_solve_csr_product(void* wq, void* csr_b, void* csr_a,
+                             void* d_eigen_vec, void* eigen_vec_host,
+                             void* eigen_val, unsigned int* iter_cnt,
+                             const st_options* opt, st_stats* stats);
+/* y = A x in the solve's row order: a reproducible SpMV on its own.  d_x and
+ * d_y device [n] in the handle's dtype, distinct; an empty row gives exactly
+ * 0.  Asynchronous on `stream`. */
+int st_csr_apply(void* csr, const void* d_x, void* d_y, void* stream);
+/* Bytes of the scratch st_csr_product_rowsum / st_csr_product_round take
+ * (256-byte aligned): x [n] at offset 0, y [n] at st_csr_product_scratch_bytes
+ * / 2; 0 for a bad n.  No GPU needed. */
+uint64_t st_csr_product_scratch_bytes(uint32_t n);
+/* "factors=2 launches_per_round=3 launches_k0=2 prep_grid=2048 x_offset=0
+ * y_offset=align256(8n) empty_rows=A".  What tools/bench_csr_product.py
+ * measures with it is in DESIGN.md, "Product operators".  No GPU needed. */
+const char* st_csr_product_shape_desc(void);
+/* The host-pointer twin with two triples (B's, then A's; n and dtype are
+ * shared): validates ON THE HOST - dtype, opt's flags, `flags`
+ * (ST_CSR_EMPTY_ROWS_OK: empty rows of A), B's triple, A's triple (messages
+ * of max_eigen_value_csr_ex behind "csr product: factor B: " / "factor A: "),
+ * then row by row that B has an entry b > 0 whose column is a row of A
+ * holding a value > 0 (the device's message; the two predicates can differ
+ * only where a product or sum under- or overflows) - copies in, solves,
+ * copies out.  Returns h2d + loop ms or negative. */
+int64_t max_eigen_value_csr_product_ex(void* wq, int dtype, uint32_t n,
+                                       uint64_t b_nnz, const int64_t* b_row_ptr,
+                                       const int32_t* b_col_idx,
+                                       const void* b_vals, uint64_t a_nnz,
+                                       const int64_t* a_row_ptr,
+                                       const int32_t* a_col_idx,
+                                       const void* a_vals, unsigned int flags,
+                                       void* eigen_val, void* eigen_vec,
+                                       unsigned int* iter_cnt,
+                                       const st_options* opt, st_stats* stats);
+/* The Gram operators of ONE host matrix: side ST_GRAM_ATA = A^T A (its
+ * eigenvalue is the square of A's spectral norm), ST_GRAM_AAT = A A^T.
+ * Validates on the host (nnz < 2^32, side, dtype, flags, the triple, then the
+ * product on a host transposition), copies A in, transposes on the device
+ * (st_csr_transpose_ex), solves, copies out.  stats->transpose_us is the
+ * transposition. */
+#define ST_GRAM_ATA 0
+#define ST_GRAM_AAT 1
+int64_t max_eigen_value_csr_gram_ex(void* wq, int dtype, uint32_t n,
+                                    uint64_t nnz, const int64_t* row_ptr,
+                                    const int32_t* col_idx, const void* vals,
+                                    int side, unsigned int flags,
+                                    void* eigen_val, void* eigen_vec,
+                                    unsigned int* iter_cnt,
+                                    const st_options* opt, st_stats* stats);
+
+/* ---------------------------------------------------------------------- */
 /* 4. step-level kernels (asynchronous on `stream`, a hipStream_t or NULL) */
 /* ---------------------------------------------------------------------- */
 
@@ -1197,6 +1282,18 @@ int st_csr_terms_round(void* csr, void* terms, const void* d_s_prev,
                        void* d_scratch, double eps, unsigned int k,
                        unsigned int max_itr, unsigned int semantics,
                        st_state* d_state, void* stream);
+/* The two steps on the product B A (section 3g; what st_solve_csr_product
+ * runs): d_scratch st_csr_product_scratch_bytes(n) bytes, 256-byte aligned.
+ * After the row sum y (the row sums of A) stands in the scratch's second
+ * half; after a round x in its first half and y = A x in its second.  s_0 is
+ * not checked here: st_solve_csr_product does that. */
+int st_csr_product_rowsum(void* csr_b, void* csr_a, void* d_s, void* d_scratch,
+                          void* stream);
+int st_csr_product_round(void* csr_b, void* csr_a, const void* d_s_prev,
+                         void* d_s_next, const void* d_v_prev, void* d_v_cur,
+                         void* d_scratch, double eps, unsigned int k,
+                         unsigned int max_itr, unsigned int semantics,
+                         st_state* d_state, void* stream);
 /* The same for the C operators of a st_csr_multi_create object (section 3f;
  * what st_solve_csr_multi runs).  All vectors are PACKED device arrays
  * [n][CP], aligned to a row of CP * b bytes; d_scratch
