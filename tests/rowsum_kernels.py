@@ -1,5 +1,6 @@
 """Drivers of every step-level kernel that computes row sums, for the exact-
-sum checks (tests/test_gpu_rowsum_exact.py, tools/rowsum_error.py).
+sum checks (tests/test_gpu_rowsum_exact.py, tools/rowsum_error.py) and the
+byte comparison with the order model (tests/test_gpu_dense_order.py).
 
 TEST INFRASTRUCTURE.  Each driver runs one kernel of eigen_value_amd.device
 on a host matrix and returns what the kernel stored and summed:
@@ -79,9 +80,44 @@ def scales(orc, n: int, dt, seed: int, unit: bool):
     return np.ascontiguousarray((orc.random_matrix(n, seed, dt, nrows=1)[0] + dt(0.5)).astype(dt))
 
 
-def run(orc, variant: str, a: np.ndarray, sem: int = SYCL, row0: int = 0, unit: bool = False):
+HALF = ("rowsum_half", "mfree_round_half")     # on a float16 / bfloat16 torch tensor
+
+
+def _run_half(variant: str, a, row0: int, s_prev, v_prev):
+    """The 16-bit kernels on the torch tensor `a` (float16 / bfloat16, on the
+    host): fp32 sums; `stored` is the matrix widened to fp32 (exact)."""
+    nrows, ncols = a.shape
+    ta = a.contiguous().to(DEV)
+    out = dict(part=None, col0=0, col1=0, stored=a.float().numpy())
+    if variant == "rowsum_half":
+        out["s"] = to_np(dev.rowsum_half(ta))
+        return out
+    assert row0 + nrows <= ncols
+    ones = np.ones(ncols, dtype=np.float32)
+    s_next = torch.full((nrows,), -1.0, dtype=torch.float32, device=DEV)
+    v_cur = torch.empty(ncols, dtype=torch.float32, device=DEV)
+    dev.mfree_round_half(ta, _dev(ones if s_prev is None else s_prev), s_next,
+                         _dev(ones if v_prev is None else v_prev), v_cur, dev.new_state(DEV),
+                         row0=row0, eps=0.0, k=1, semantics=SYCL)
+    out["s"] = to_np(s_next)
+    return out
+
+
+def run(orc, variant: str, a: np.ndarray, sem: int = SYCL, row0: int = 0, unit: bool = False, *,
+        s_prev=None, v_prev=None, scale=None, rounds: bool = False):
     """Run `variant` on the host matrix `a` (nrows x ncols) as rows row0 ...
-    of the s vector.  Returns dict(stored, s, part, col0, col1)."""
+    of the s vector.  Returns dict(stored, s, part, col0, col1).
+
+    scale: the scale vector s_cur instead of `scales(orc, ...)` (the deferred
+    variants: the list of their npend + 1 vectors).  s_prev / v_prev: those of
+    the matrix-free variants instead of ones.  rounds (deferred variants):
+    also s_rounds / part_rounds, every round's s_next and partials, and
+    pend_s / pend_inv, the rounds' scales and the reciprocals the device made
+    of them.  split_flat_round also returns split_part, its whole scratch (the
+    remote partials, then the local ones: device.split_flat_scratch).  The
+    variants of HALF take a float16 / bfloat16 torch tensor."""
+    if variant in HALF:
+        return _run_half(variant, a, row0, s_prev, v_prev)
     dt = a.dtype.type
     tdt = TD[a.dtype]
     nrows, ncols = a.shape
@@ -97,11 +133,14 @@ def run(orc, variant: str, a: np.ndarray, sem: int = SYCL, row0: int = 0, unit: 
         dev.rowsum_flat(ta, s_next, part)
         out["part"] = part
     elif variant == "scale_rowsum":
-        dev.scale_rowsum(ta, _dev(scales(orc, n_full, dt, 9, unit)), s_next, row0=row0,
-                         semantics=sem)
+        dev.scale_rowsum(ta, _dev(scales(orc, n_full, dt, 9, unit) if scale is None else scale),
+                         s_next, row0=row0, semantics=sem)
     else:
         assert row0 + nrows <= ncols
-        ts = _dev(scales(orc, ncols, dt, 9, unit))
+        deferred = variant.startswith("flat_round_deferred")
+        ts = None
+        if not deferred:
+            ts = _dev(scales(orc, ncols, dt, 9, unit) if scale is None else scale)
         tv = torch.ones(ncols, dtype=tdt, device=DEV)
         state = dev.new_state(DEV)
         if variant == "fused_round":
@@ -110,12 +149,13 @@ def run(orc, variant: str, a: np.ndarray, sem: int = SYCL, row0: int = 0, unit: 
             part = dev.flat_scratch(nrows, ncols, tdt, DEV)
             dev.flat_round(ta, ts, s_next, part, tv, state, k=0, **kw)
             out["part"] = part
-        elif variant.startswith("flat_round_deferred"):
+        elif deferred:
             # as tests/test_gpu_deferred_step.py drives it: `npend` read-only
             # rounds from A_0, then the storing round; ta ends at A_{npend+1}
             npend = int(variant[-1])
             part = dev.flat_scratch(nrows, ncols, tdt, DEV)
-            s = [_dev(scales(orc, ncols, dt, 9 + k, unit)) for k in range(npend + 1)]
+            s = [_dev(scales(orc, ncols, dt, 9 + k, unit) if scale is None else scale[k])
+                 for k in range(npend + 1)]
             inv = [torch.empty_like(x) for x in s]
             for x, y in zip(s, inv):
                 dev.recip(x, y)
@@ -123,6 +163,11 @@ def run(orc, variant: str, a: np.ndarray, sem: int = SYCL, row0: int = 0, unit: 
             for k in range(npend + 1):
                 dev.flat_round_deferred(ta, s[k], inv[k], s_next, inv_next, part, tv, state,
                                         s[:k], inv[:k], store=k == npend, k=k, **kw)
+                if rounds:
+                    out.setdefault("s_rounds", []).append(to_np(s_next))
+                    out.setdefault("part_rounds", []).append(to_np(part))
+            if rounds:
+                out.update(pend_s=[to_np(x) for x in s], pend_inv=[to_np(x) for x in inv])
             out["part"] = part
         elif variant in ("split_round", "split_flat_round"):
             col0, col1 = row0, row0 + nrows                # the block's own rows
@@ -136,16 +181,21 @@ def run(orc, variant: str, a: np.ndarray, sem: int = SYCL, row0: int = 0, unit: 
                **kw)
             fn(ta, ts, s_next, part, tv, state, span=dev.SPAN_REMOTE, col0=col0, col1=col1, k=0,
                **kw)
+            if variant == "split_flat_round":              # both partial buffers, as laid out
+                out["split_part"] = to_np(part)
         elif variant in ("mfree_round", "mfree_round_flat"):
             # launch k = 1 with s_prev = v_prev = 1: x = v s = 1, every product
             # A_0[r][c] x[c] is exact and s_next = (sum) / 1 a pure row sum of A_0
+            # (or the caller's s_prev / v_prev: a rounded x)
             ones = torch.ones(ncols, dtype=tdt, device=DEV)
+            tsp = ones if s_prev is None else _dev(s_prev)
+            tvp = tv if v_prev is None else _dev(v_prev)
             v_cur = torch.empty_like(ones)
             if variant == "mfree_round":
-                dev.mfree_round(ta, ones, s_next, tv, v_cur, state, k=1, **kw)
+                dev.mfree_round(ta, tsp, s_next, tvp, v_cur, state, k=1, **kw)
             else:
                 part = dev.flat_scratch(nrows, ncols, tdt, DEV)
-                dev.mfree_round_flat(ta, ones, s_next, tv, v_cur, part, state, k=1, **kw)
+                dev.mfree_round_flat(ta, tsp, s_next, tvp, v_cur, part, state, k=1, **kw)
                 out["part"] = part
         else:
             raise ValueError(variant)
@@ -154,6 +204,8 @@ def run(orc, variant: str, a: np.ndarray, sem: int = SYCL, row0: int = 0, unit: 
     if out["part"] is not None:
         ppr = xs.pieces_per_row(a.dtype, ncols)
         out["part"] = to_np(out["part"])[:nrows * ppr].reshape(nrows, ppr)
+        if rounds and "part_rounds" in out:
+            out["part_rounds"] = [p[:nrows * ppr].reshape(nrows, ppr) for p in out["part_rounds"]]
     return out
 
 
