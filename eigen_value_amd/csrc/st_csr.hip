@@ -408,10 +408,11 @@ st_csr_shape_desc(void)
                   st::csr::kUnroll[0] == 1 && st::csr::kUnroll[1] == 2 &&
                   st::csr::kUnroll[2] == 4 && st::csr::kUnroll[3] == 8 &&
                   st::csr::kNnzMax[0] == 16 && st::csr::kNnzMax[1] == 128 &&
-                  st::csr::kNnzMax[2] == 2048,
+                  st::csr::kNnzMax[2] == 2048 && st::kCsrPrepGrid == 2048 &&
+                  st::kCsrCheckGrid == 8192,
                 "the description below");
   return "lanes=4,16,64,256 nnz_max=16,128,2048,inf rows=8,4,2,1 "
-         "unroll=1,2,4,8 prep_grid=2048";
+         "unroll=1,2,4,8 prep_grid=2048 check_grid=8192";
 }
 
 int

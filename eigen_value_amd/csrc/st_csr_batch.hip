@@ -382,11 +382,13 @@ extern "C" {
 const char*
 st_csr_batch_shape_desc(void)
 {
-  static_assert(st::kCsrbPrepCap == 2048 && st::kCsrbCollectGrid == 2048,
+  static_assert(st::kCsrbPrepCap == 2048 && st::kCsrbCollectGrid == 2048 &&
+                  st::kCsrbCheckGrid == 8192,
                 "the description below");
   return "prep: 1 workgroup per 256 rows of a matrix, at most 2048 per matrix, "
          "no workgroup shared by two matrices; spmv: st_csr_shape_desc over the "
-         "stacked rows; collect_grid=2048";
+         "stacked rows; collect_grid=2048; check: 16 lanes per row, at most 8192 "
+         "workgroups";
 }
 
 int

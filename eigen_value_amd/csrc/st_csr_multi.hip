@@ -472,12 +472,13 @@ st_csr_multi_shape_desc(void)
 {
   static_assert(st::dev::kCsrDotGrid == 2048 && st::csr::kTermsMax == 4 &&
                   st::csr::kMultiMax == 8 && st::csr::multi_cp(3) == 4 &&
-                  st::csr::multi_rows(0, 64) == 2 && st::csr::multi_unroll(3, 32) == 4,
+                  st::csr::multi_rows(0, 64) == 2 && st::csr::multi_unroll(3, 32) == 4 &&
+                  st::kCheckGrid == 8192,
                 "the description below");
   return "multi_max=8 terms_max=4 widths=2,4,8 dot_grid=2048 lanes=256 "
          "combine=one_workgroup_per_column launches_per_round=3 dots_offset=0 "
          "partial_offset=256 rows16=8,4,2,1 unroll16=1,2,4,8 rows32=4,2,1,1 "
-         "unroll32=1,2,4,4 rows64=2,2,1,1 unroll64=1,1,2,2";
+         "unroll32=1,2,4,4 rows64=2,2,1,1 unroll64=1,1,2,2 check_grid=8192";
 }
 
 int

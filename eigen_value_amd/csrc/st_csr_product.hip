@@ -195,9 +195,10 @@ st_csr_product_scratch_bytes(uint32_t n)
 const char*
 st_csr_product_shape_desc(void)
 {
-  static_assert(st::kCsrPrepGrid == 2048, "the description below");
+  static_assert(st::kCsrPrepGrid == 2048 && st::kCheckGrid == 8192,
+                "the description below");
   return "factors=2 launches_per_round=3 launches_k0=2 prep_grid=2048 "
-         "x_offset=0 y_offset=align256(8n) empty_rows=A";
+         "x_offset=0 y_offset=align256(8n) empty_rows=A check_grid=8192";
 }
 
 int

@@ -400,10 +400,11 @@ st_csr_terms_scratch_bytes(uint32_t n, uint32_t K)
 const char*
 st_csr_terms_shape_desc(void)
 {
-  static_assert(st::dev::kCsrDotGrid == 2048 && st::csr::kTermsMax == 4,
+  static_assert(st::dev::kCsrDotGrid == 2048 && st::csr::kTermsMax == 4 &&
+                  st::kCheckGrid == 8192,
                 "the description below");
   return "terms_max=4 dot_grid=2048 lanes=256 combine=one_workgroup "
-         "launches_per_round=3 dots_offset=0 partial_offset=256";
+         "launches_per_round=3 dots_offset=0 partial_offset=256 check_grid=8192";
 }
 
 int

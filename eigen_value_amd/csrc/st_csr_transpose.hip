@@ -313,9 +313,11 @@ const char*
 st_csr_transpose_shape_desc(void)
 {
   static_assert(st::dev::kDigitBits == 8 && st::dev::kTile == 2048 &&
-                  st::dev::kTileRounds == 8 && st::dev::kColsPerBlock == 2048,
+                  st::dev::kTileRounds == 8 && st::dev::kColsPerBlock == 2048 &&
+                  st::kTrGrid == 8192,
                 "the description below");
-  return "digit_bits=8 tile=2048 rounds=8 lanes=256 col_block=2048 payload=index";
+  return "digit_bits=8 tile=2048 rounds=8 lanes=256 col_block=2048 payload=index "
+         "grid=8192";
 }
 
 } // extern "C"

@@ -467,9 +467,10 @@ int st_csr_class_limits(int dtype, uint32_t* nnz_max, uint32_t* lanes, int cap);
 int st_csr_plan(const int64_t* row_ptr, uint32_t n, uint32_t* order_out,
                 uint32_t* class_first);
 /* The shape the CSR kernels were built with ("lanes=4,16,64,256
- * nnz_max=16,128,2048,inf rows=8,4,2,1 unroll=1,2,4,8 prep_grid=2048": lanes
- * per row and nnz limit of each class, rows the lanes of a row take side by
- * side and entries of each in flight, the workgroup cap of the vector pass);
+ * nnz_max=16,128,2048,inf rows=8,4,2,1 unroll=1,2,4,8 prep_grid=2048
+ * check_grid=8192": lanes per row and nnz limit of each class, rows the lanes
+ * of a row take side by side and entries of each in flight, the workgroup cap
+ * of the vector pass and of the create-time column check);
  * tools record it next to their numbers.  On MI355X (tools/bench_csr.py,
  * profiles/csr_solve.json, one interleaved run, n = 4194304): 0.633 / 1.981 /
  * 7.702 ms per fp32 round at 8 / 32 / 128 random columns per row (715 / 635 /
@@ -563,9 +564,10 @@ int st_csr_transpose(void* wq, void* csr, int64_t* d_t_row_ptr,
  * nnz >= 2^32.  No GPU needed. */
 uint64_t st_csr_transpose_scratch_bytes(uint32_t n, uint64_t nnz);
 /* The shape the transposition was built with ("digit_bits=8 tile=2048
- * rounds=8 lanes=256 col_block=2048 payload=index": bits per pass, entries
- * per workgroup = rounds x lanes, columns per workgroup of the t_row_ptr
- * scan, what travels with the key).  What tools/bench_csr_transpose.py
+ * rounds=8 lanes=256 col_block=2048 payload=index grid=8192": bits per pass,
+ * entries per workgroup = rounds x lanes, columns per workgroup of the
+ * t_row_ptr scan, what travels with the key, the workgroup cap of the count
+ * and the gather).  What tools/bench_csr_transpose.py
  * measured with it is in DESIGN.md, "Transposed CSR".  No GPU needed. */
 const char* st_csr_transpose_shape_desc(void);
 /* max_eigen_value_csr_ex for the LEFT vector: validates on the host (nnz <
@@ -627,7 +629,9 @@ int st_csr_batch_destroy(void* h);
 int st_csr_batch_get_plan(void* h, uint32_t* order_out, uint32_t* class_first);
 /* The launch shape of the batch kernels, for tools to record
  * (tools/bench_csr_batched.py; what it measured is in DESIGN.md, "Batched
- * sparse solve").  No GPU needed. */
+ * sparse solve"); it ends with the caps of the create-time column check (16
+ * lanes per row, at most 8192 workgroups) and of the collect pass
+ * (collect_grid=2048).  No GPU needed. */
 const char* st_csr_batch_shape_desc(void);
 /* The solve.  d_eigen_vecs device [N] or NULL, then eigen_vecs_host receives
  * the stacked eigenvectors; eigen_vals (the handle's dtype), iter_cnts and
@@ -726,7 +730,8 @@ int st_csr_terms_destroy(void* terms);
  * [n] behind them; 0 for a bad n or K.  No GPU needed. */
 uint64_t st_csr_terms_scratch_bytes(uint32_t n, uint32_t K);
 /* "terms_max=4 dot_grid=2048 lanes=256 combine=one_workgroup
- * launches_per_round=3 dots_offset=0 partial_offset=256".  What
+ * launches_per_round=3 dots_offset=0 partial_offset=256 check_grid=8192"
+ * (check_grid: the workgroup cap of the create-time checks).  What
  * tools/bench_csr_terms.py measured with it is in DESIGN.md, "Low-rank terms
  * and empty rows".  No GPU needed. */
 const char* st_csr_terms_shape_desc(void);
@@ -787,7 +792,8 @@ uint64_t st_csr_multi_scratch_bytes(uint32_t n, uint32_t C, uint32_t K);
 /* "multi_max=8 terms_max=4 widths=2,4,8 dot_grid=2048 lanes=256
  * combine=one_workgroup_per_column launches_per_round=3 dots_offset=0
  * partial_offset=256 rows16=... unroll16=... rows32=... unroll32=... rows64=...
- * unroll64=...": rowsB / unrollB are the rows side by side and the entries in
+ * unroll64=... check_grid=8192": check_grid is the workgroup cap of the
+ * create-time passes (pack, checks, collect); rowsB / unrollB are the rows side by side and the entries in
  * flight per lane of the four row classes when a packed row is B = CP * b
  * bytes.  What tools/bench_csr_multi.py measured with it is in DESIGN.md,
  * "Many term sets on one matrix".  No GPU needed. */
@@ -862,7 +868,8 @@ int st_csr_apply(void* csr, const void* d_x, void* d_y, void* stream);
  * / 2; 0 for a bad n.  No GPU needed. */
 uint64_t st_csr_product_scratch_bytes(uint32_t n);
 /* "factors=2 launches_per_round=3 launches_k0=2 prep_grid=2048 x_offset=0
- * y_offset=align256(8n) empty_rows=A".  What tools/bench_csr_product.py
+ * y_offset=align256(8n) empty_rows=A check_grid=8192" (check_grid: the
+ * workgroup cap of the s_0 check).  What tools/bench_csr_product.py
  * measures with it is in DESIGN.md, "Product operators".  No GPU needed. */
 const char* st_csr_product_shape_desc(void);
 /* The host-pointer twin with two triples (B's, then A's; n and dtype are
