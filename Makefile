@@ -11,7 +11,7 @@ SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hi
             eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip \
             eigen_value_amd/csrc/st_csr_batch.hip eigen_value_amd/csrc/st_csr_transpose.hip \
             eigen_value_amd/csrc/st_csr_terms.hip eigen_value_amd/csrc/st_csr_multi.hip \
-            eigen_value_amd/csrc/st_csr_product.hip
+            eigen_value_amd/csrc/st_csr_product.hip eigen_value_amd/csrc/st_csr_pattern.hip
 OBJ     := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
@@ -25,7 +25,7 @@ HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/c
             eigen_value_amd/csrc/st_csr_host.h eigen_value_amd/csrc/st_csr_batch.h \
             eigen_value_amd/csrc/st_csr_plan.h eigen_value_amd/csrc/st_csr_transpose.h \
             eigen_value_amd/csrc/st_csr_terms.h eigen_value_amd/csrc/st_csr_multi.h \
-            eigen_value_amd/csrc/st_csr_product.h
+            eigen_value_amd/csrc/st_csr_product.h eigen_value_amd/csrc/st_csr_pattern.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 
@@ -97,8 +97,21 @@ csr_product_sanitize: $(LIB) tests/cpp/csr_product_sanitize.cpp eigen_value_amd/
 	./build/csr_product_sanitize build/csr_tables/table0.bin build/csr_tables/table1.bin \
 	  build/csr_tables/table2.bin
 
+# the host side of the pattern-only operator (st_csr_host.h: the scales'
+# predicate and messages, the pattern's host check and the rows of the operator
+# with terms) under the host sanitizers, as csr_terms_sanitize
+csr_pattern_sanitize: $(LIB) tests/cpp/csr_pattern_sanitize.cpp eigen_value_amd/csrc/st_csr_host.h
+	@mkdir -p build/csr_tables
+	$(PYTHON) tests/csr_cases.py build/csr_tables
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	  -fno-omit-frame-pointer -Ieigen_value_amd/csrc tests/cpp/csr_pattern_sanitize.cpp \
+	  -o build/csr_pattern_sanitize
+	./build/csr_pattern_sanitize build/csr_tables/table0.bin build/csr_tables/table1.bin \
+	  build/csr_tables/table2.bin
+
 clean:
 	rm -rf build eigen_value_amd/lib
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean probe csr_terms_sanitize csr_multi_sanitize csr_product_sanitize
+.PHONY: all oracle clean probe csr_terms_sanitize csr_multi_sanitize csr_product_sanitize \
+        csr_pattern_sanitize

@@ -364,6 +364,34 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_csr_terms_rowsum.restype = i32
     L.st_csr_terms_round.argtypes = [P, P, P, P, P, P, P, f64, u32, u32, u32, P, P]
     L.st_csr_terms_round.restype = i32
+    # pattern-only matrices with row / column scales
+    L.st_csr_pattern_create.argtypes = [P, i32, u32, u64, P, P, P, P, u32,
+                                        ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_pattern_create.restype = i32
+    L.st_csr_pattern_destroy.argtypes = [P]
+    L.st_csr_pattern_destroy.restype = i32
+    L.st_csr_pattern_get_plan.argtypes = [P, P, P]
+    L.st_csr_pattern_get_plan.restype = i32
+    L.st_csr_pattern_empty_rows.argtypes = [P, P, P]
+    L.st_csr_pattern_empty_rows.restype = i32
+    L.st_csr_pattern_transpose.argtypes = [P, P, P, P, u32, ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_pattern_transpose.restype = i32
+    L.st_csr_pattern_terms_create.argtypes = [P, P, u32, P, P,
+                                              ctypes.POINTER(ctypes.c_void_p)]
+    L.st_csr_pattern_terms_create.restype = i32
+    L.st_solve_csr_pattern.argtypes = [P, P, P, P, P, P, P, P, P]
+    L.st_solve_csr_pattern.restype = i64
+    L.st_csr_pattern_scratch_bytes.argtypes = [u32, u32]
+    L.st_csr_pattern_scratch_bytes.restype = u64
+    L.st_csr_pattern_shape_desc.argtypes = []
+    L.st_csr_pattern_shape_desc.restype = ctypes.c_char_p
+    L.st_csr_pattern_rowsum.argtypes = [P, P, P, P, P]
+    L.st_csr_pattern_rowsum.restype = i32
+    L.st_csr_pattern_round.argtypes = [P, P, P, P, P, P, P, f64, u32, u32, u32, P, P]
+    L.st_csr_pattern_round.restype = i32
+    L.max_eigen_value_csr_pattern_ex.argtypes = [P, i32, u32, u64, P, P, P, P, u32, P, P,
+                                                 u32, P, P, P, P, P]
+    L.max_eigen_value_csr_pattern_ex.restype = i64
     L.st_csr_multi_create.argtypes = [P, P, u32, u32, P, P, ctypes.POINTER(ctypes.c_void_p)]
     L.st_csr_multi_create.restype = i32
     L.st_csr_multi_destroy.argtypes = [P]
@@ -530,6 +558,23 @@ def csr_terms_shape(L: Optional[ctypes.CDLL] = None) -> dict:
     L = L or load()
     out = {}
     for item in L.st_csr_terms_shape_desc().decode().split():
+        k, v = item.split("=")
+        out[k] = int(v) if v.isdigit() else v
+    return out
+
+
+CSR_PATTERN_SYMBOLS = (
+    "st_csr_pattern_create", "st_csr_pattern_destroy", "st_csr_pattern_get_plan",
+    "st_csr_pattern_empty_rows", "st_csr_pattern_transpose", "st_csr_pattern_terms_create",
+    "st_solve_csr_pattern", "st_csr_pattern_scratch_bytes", "st_csr_pattern_shape_desc",
+    "st_csr_pattern_rowsum", "st_csr_pattern_round", "max_eigen_value_csr_pattern_ex")
+
+
+def csr_pattern_shape(L: Optional[ctypes.CDLL] = None) -> dict:
+    """st_csr_pattern_shape_desc as a dict (integers where they are)."""
+    L = L or load()
+    out = {}
+    for item in L.st_csr_pattern_shape_desc().decode().split():
         k, v = item.split("=")
         out[k] = int(v) if v.isdigit() else v
     return out

@@ -157,6 +157,30 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   ST_REQUIRE(((uintptr_t)d_row_ptr & 7u) == 0 && ((uintptr_t)d_col_idx & 3u) == 0 &&
                ((uintptr_t)d_vals & (dtype ? 7u : 3u)) == 0,
              "csr: an array is not aligned to its element size");
+  Scratch mem; // [0] order, until the handle takes it
+  uint32_t* d_order = nullptr;
+  uint32_t cf[csr::kClasses + 1];
+  uint32_t empty_rows = 0, first_empty = n;
+  if (csr_check_and_plan(n, nnz, d_row_ptr, d_col_idx, stream, empty_ok, &d_order, cf,
+                         &empty_rows, &first_empty))
+    return -1;
+  mem.p[0] = d_order;
+  CsrHandle* h = nullptr;
+  if (csr_make_handle(dtype, n, nnz, d_row_ptr, d_col_idx, d_vals, d_order, cf, &h,
+                      empty_rows, first_empty))
+    return -1;
+  mem.p[0] = nullptr; // the handle's now
+  *out = h;
+  return 0;
+}
+
+int
+csr_check_and_plan(uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
+                   const int32_t* d_col_idx, hipStream_t stream, bool empty_ok,
+                   uint32_t** d_order_out, uint32_t* cf, uint32_t* empty_rows_out,
+                   uint32_t* first_empty_out)
+{
+  *d_order_out = nullptr;
   const uint32_t nblk = (n + kBlock - 1) / kBlock;
   Scratch mem; // [0] err (2 words) + class_first (5), [1] cnt, [2] order
   ST_CHECK(hipMalloc(&mem.p[0], 2 * sizeof(unsigned long long) + 8 * sizeof(uint32_t)));
@@ -227,15 +251,13 @@ csr_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
   ST_CHECK(hipMemsetAsync(d_order, 0, sizeof(uint32_t) * (size_t)n, stream));
   if (launch_csr_plan(d_row_ptr, n, d_cnt, d_cf, d_order, stream))
     return -1;
-  uint32_t cf[csr::kClasses + 1];
-  ST_CHECK(hipMemcpyAsync(cf, d_cf, sizeof(cf), hipMemcpyDeviceToHost, stream));
+  ST_CHECK(hipMemcpyAsync(cf, d_cf, sizeof(uint32_t) * (csr::kClasses + 1),
+                          hipMemcpyDeviceToHost, stream));
   ST_CHECK(hipStreamSynchronize(stream));
-  CsrHandle* h = nullptr;
-  if (csr_make_handle(dtype, n, nnz, d_row_ptr, d_col_idx, d_vals, d_order, cf, &h,
-                      empty_rows, first_empty))
-    return -1;
-  mem.p[2] = nullptr; // the handle's now
-  *out = h;
+  mem.p[2] = nullptr; // the caller's now
+  *d_order_out = d_order;
+  *empty_rows_out = empty_rows;
+  *first_empty_out = first_empty;
   return 0;
 }
 

@@ -4,8 +4,9 @@
 // into a stand-alone program (tests/cpp/csr_sanitize.cpp and, for the empty
 // rows flag and the low-rank terms, tests/cpp/csr_terms_sanitize.cpp, for the
 // multi-column packing and validation tests/cpp/csr_multi_sanitize.cpp, for
-// the product operator tests/cpp/csr_product_sanitize.cpp, run under the host
-// sanitizers).  Included by st_csr.hip; not a public header.
+// the product operator tests/cpp/csr_product_sanitize.cpp, for the pattern-only
+// operator tests/cpp/csr_pattern_sanitize.cpp, run under the host sanitizers).
+// Included by st_csr.hip; not a public header.
 //
 // Every function returns 0 (or a count) on success and -1 on failure with
 // the reason written to msg[cap].
@@ -730,6 +731,125 @@ batch_prep_wgs(uint32_t n_b, uint32_t prep_cap)
 {
   const uint32_t want = (n_b + kBlock - 1) / kBlock;
   return want < prep_cap ? want : prep_cap;
+}
+
+// ---------------------------------------------------------------------------
+// The pattern-only operator M = diag(r) P diag(c) (st_csr_pattern.hip): P the
+// 0/1 pattern of row_ptr / col_idx (duplicates count), r and c dense vectors
+// [n], each null (all ones) or finite and > 0.  The device check applies the
+// same predicates in the same order - row_ptr, the columns, then the scales,
+// row_scale before col_scale, the lowest index - and prints through the same
+// describe_* functions (tests/cpp/csr_pattern_sanitize.cpp runs these under
+// the host sanitizers).
+// ---------------------------------------------------------------------------
+// finite and > 0 (NaN fails every comparison)
+template <typename T>
+inline bool
+scale_entry_bad(T x)
+{
+  return !(x > (T)0) || x - x != (T)0; // inf - inf is NaN
+}
+
+// which: 0 = row_scale, 1 = col_scale
+inline void
+describe_scale_entry(int which, uint32_t i, double x, char* msg, size_t cap)
+{
+  snprintf(msg, cap, "csr pattern: %s[%u] = %g is not finite and positive",
+           which ? "col_scale" : "row_scale", i, x);
+}
+
+// either vector may be null
+template <typename T>
+inline int
+check_pattern_scales(uint32_t n, const T* r, const T* c, char* msg, size_t cap)
+{
+  for (int which = 0; which < 2; which++) {
+    const T* p = which ? c : r;
+    if (!p)
+      continue;
+    for (uint32_t i = 0; i < n; i++)
+      if (scale_entry_bad<T>(p[i])) {
+        describe_scale_entry(which, i, (double)p[i], msg, cap);
+        return -1;
+      }
+  }
+  return 0;
+}
+
+// check_host without values
+inline int
+check_pattern_host(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
+                   const int32_t* col_idx, char* msg, size_t cap, bool empty_ok = false)
+{
+  if (dtype != 0 && dtype != 1) {
+    snprintf(msg, cap, "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+    return -1;
+  }
+  if (n == 0 || n >= 0x80000000u) {
+    snprintf(msg, cap, "csr: n must be in [1, 2^31), got %u", n);
+    return -1;
+  }
+  if (empty_ok && check_nnz_min(nnz, msg, cap))
+    return -1;
+  if (!row_ptr || !col_idx) {
+    snprintf(msg, cap, "csr: null row_ptr / col_idx");
+    return -1;
+  }
+  if (check_row_ptr(row_ptr, n, true, nnz, msg, cap, empty_ok))
+    return -1;
+  return check_col_idx(row_ptr, col_idx, n, nnz, msg, cap);
+}
+
+// the terms of a pattern operator: none (K = 0) is legal
+inline int
+check_pattern_terms_count(uint32_t K, char* msg, size_t cap)
+{
+  if (K > kTermsMax) {
+    snprintf(msg, cap, "csr pattern: K must be in [0, %u], got %u", kTermsMax, K);
+    return -1;
+  }
+  return 0;
+}
+
+// what a pattern solve without terms says to an empty-rows handle
+inline void
+describe_pattern_needs_terms(const char* what, uint32_t r, uint32_t count, char* msg,
+                             size_t cap)
+{
+  snprintf(msg, cap,
+           "%s: row %u is empty (%u empty rows, ST_CSR_EMPTY_ROWS_OK): its row "
+           "sum would be divided by zero; such a pattern is solved with "
+           "low-rank terms (st_csr_pattern_terms_create)", what, r, count);
+}
+
+// check_terms_rows on the pattern operator: s_0[i] = r[i] * sum_e c[col[e]] +
+// sum_j u_j[i] (w_j . 1), finite and > 0 (summed in double here; the device
+// judges the s_0 its own launch 0 computes)
+template <typename T>
+inline int
+check_pattern_terms_rows(uint32_t n, const int64_t* row_ptr, const int32_t* col_idx,
+                         const T* r, const T* c, uint32_t K, const T* const* u,
+                         const T* const* w, char* msg, size_t cap)
+{
+  double d[kTermsMax] = { 0, 0, 0, 0 };
+  for (uint32_t j = 0; j < K; j++)
+    for (uint32_t i = 0; i < n; i++)
+      d[j] += (double)w[j][i];
+  for (uint32_t i = 0; i < n; i++) {
+    double s = 0;
+    for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; e++)
+      s += c ? (double)c[(uint32_t)col_idx[e]] : 1.0;
+    if (r)
+      s *= (double)r[i];
+    for (uint32_t j = 0; j < K; j++)
+      s += (double)u[j][i] * d[j];
+    const T st = (T)s;
+    if (!(st > (T)0) || st - st != (T)0) {
+      describe_term_row(i, (double)st, msg, cap);
+      return -1;
+    }
+  }
+  return 0;
 }
 
 } // namespace csr

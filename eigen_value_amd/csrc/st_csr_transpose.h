@@ -27,6 +27,7 @@
 //                   the tiles before it from the scanned table
 //   k_tr_gather     t_vals[i] = vals[perm[i]], t_col_idx[i] = the row of
 //                   entry perm[i] (bisection of row_ptr)
+//   k_tr_gather_rows  the same without values (st_csr_pattern_transpose)
 //
 // No workgroup waits on another anywhere: every dependency is a launch
 // boundary.  Every computed destination is bounded, so that a matrix changed
@@ -288,6 +289,29 @@ k_tr_gather(const int64_t* __restrict__ row_ptr, const T* __restrict__ vals,
     }
     t_col[i] = (int32_t)lo;
     t_vals[i] = vals[e];
+  }
+}
+
+// k_tr_gather without values (a pattern handle): the source rows only
+__global__ __launch_bounds__(kBlock) void
+k_tr_gather_rows(const int64_t* __restrict__ row_ptr,
+                 const uint32_t* __restrict__ perm, uint32_t n, uint64_t nnz,
+                 int32_t* __restrict__ t_col)
+{
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nnz;
+       i += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t e = perm ? (uint64_t)perm[i] : i;
+    if (e >= nnz) // never, for a matrix that did not change
+      continue;
+    uint32_t lo = 0, hi = n; // the row with row_ptr[lo] <= e < row_ptr[lo + 1]
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if ((uint64_t)row_ptr[mid] <= e)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    t_col[i] = (int32_t)lo;
   }
 }
 

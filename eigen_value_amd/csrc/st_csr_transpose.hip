@@ -117,29 +117,60 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
 {
   ST_REQUIRE(out, "st_csr_transpose: null output pointer");
   *out = nullptr;
+  Freed order;
+  uint32_t* d_order = nullptr;
+  uint32_t cf[csr::kClasses + 1];
+  uint32_t empty_rows = 0, first_empty = a->n;
+  if (csr_transpose_arrays(a->dtype, a->n, a->nnz, a->row_ptr, a->col_idx, a->vals,
+                           d_t_row_ptr, d_t_col_idx, d_t_vals, stream, flags, &d_order,
+                           cf, &empty_rows, &first_empty))
+    return -1;
+  order.p = d_order;
+  CsrHandle* h = nullptr;
+  if (csr_make_handle(a->dtype, a->n, a->nnz, d_t_row_ptr, d_t_col_idx, d_t_vals,
+                      d_order, cf, &h, empty_rows, first_empty))
+    return -1;
+  order.p = nullptr; // the handle's now
+  *out = h;
+  return 0;
+}
+
+// vals == nullptr (a pattern handle): two arrays in, two out, the final
+// gather writes source rows only
+int
+csr_transpose_arrays(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
+                     const int32_t* col_idx, const void* vals, int64_t* d_t_row_ptr,
+                     int32_t* d_t_col_idx, void* d_t_vals, hipStream_t stream,
+                     uint32_t flags, uint32_t** d_order_out, uint32_t* cf,
+                     uint32_t* empty_rows_out, uint32_t* first_empty_out)
+{
+  *d_order_out = nullptr;
+  const bool pattern = vals == nullptr;
   ST_REQUIRE((flags & ~csr::kEmptyRowsOk) == 0,
              "st_csr_transpose_ex: unknown flags %u", flags);
   const bool empty_ok = (flags & csr::kEmptyRowsOk) != 0;
   char msg[384];
-  if (csr::check_transpose_nnz(a->nnz, msg, sizeof(msg))) {
+  if (csr::check_transpose_nnz(nnz, msg, sizeof(msg))) {
     set_error("%s", msg);
     return -1;
   }
-  ST_REQUIRE(d_t_row_ptr && d_t_col_idx && d_t_vals,
-             "csr transpose: null t_row_ptr / t_col_idx / t_vals");
-  const uint32_t n = a->n;
-  const uint64_t nnz = a->nnz;
-  const size_t elem = a->dtype ? 8 : 4;
+  if (pattern)
+    ST_REQUIRE(d_t_row_ptr && d_t_col_idx, "csr transpose: null t_row_ptr / t_col_idx");
+  else
+    ST_REQUIRE(d_t_row_ptr && d_t_col_idx && d_t_vals,
+               "csr transpose: null t_row_ptr / t_col_idx / t_vals");
+  const size_t elem = dtype ? 8 : 4;
   ST_REQUIRE(((uintptr_t)d_t_row_ptr & 7u) == 0 && ((uintptr_t)d_t_col_idx & 3u) == 0 &&
-               ((uintptr_t)d_t_vals & (elem - 1)) == 0,
+               (pattern || ((uintptr_t)d_t_vals & (elem - 1)) == 0),
              "csr: an array is not aligned to its element size");
   {
-    const void* in[3] = { a->row_ptr, a->col_idx, a->vals };
+    const int na = pattern ? 2 : 3; // the arrays on each side
+    const void* in[3] = { row_ptr, col_idx, vals };
     const void* o[3] = { d_t_row_ptr, d_t_col_idx, d_t_vals };
     const size_t sz[3] = { 8 * ((size_t)n + 1), 4 * (size_t)nnz, elem * (size_t)nnz };
     static const char* const name[3] = { "row_ptr", "col_idx", "vals" };
-    for (int i = 0; i < 3; i++) {
-      for (int j = 0; j < 3; j++)
+    for (int i = 0; i < na; i++) {
+      for (int j = 0; j < na; j++)
         ST_REQUIRE(!overlap(o[i], sz[i], in[j], sz[j]),
                    "csr transpose: the output t_%s overlaps the input %s: the "
                    "transposition is not done in place", name[i], name[j]);
@@ -179,7 +210,7 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
   ST_CHECK(hipMemsetAsync(d_dtot, 0, sizeof(uint32_t) * dev::kDigits *
                                        (lay.passes ? lay.passes : 1), stream));
   hipLaunchKernelGGL(dev::k_tr_count, dim3(egrid), dim3(kBlock), 0, stream,
-                     a->col_idx, n, nnz, d_cnt);
+                     col_idx, n, nnz, d_cnt);
   if (check_launch("tr_count"))
     return -1;
   hipLaunchKernelGGL(dev::k_tr_colsum, dim3(lay.ncb), dim3(kBlock), 0, stream,
@@ -206,7 +237,7 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
     return -1;
 
   // 2. the digit passes: pass p sorts by bits [8 p, 8 p + 8) of the column
-  const uint32_t* keys_in = reinterpret_cast<const uint32_t*>(a->col_idx);
+  const uint32_t* keys_in = reinterpret_cast<const uint32_t*>(col_idx);
   const uint32_t* idx_in = nullptr;
   for (uint32_t p = 0; p < lay.passes; p++) {
     const uint32_t shift = p * dev::kDigitBits;
@@ -230,13 +261,16 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
   }
 
   // 3. the values and the source rows through the permutation
-  if (a->dtype)
+  if (pattern)
+    hipLaunchKernelGGL(dev::k_tr_gather_rows, dim3(egrid), dim3(kBlock), 0, stream,
+                       row_ptr, idx_in, n, nnz, d_t_col_idx);
+  else if (dtype)
     hipLaunchKernelGGL(dev::k_tr_gather<double>, dim3(egrid), dim3(kBlock), 0,
-                       stream, a->row_ptr, static_cast<const double*>(a->vals),
+                       stream, row_ptr, static_cast<const double*>(vals),
                        idx_in, n, nnz, d_t_col_idx, static_cast<double*>(d_t_vals));
   else
     hipLaunchKernelGGL(dev::k_tr_gather<float>, dim3(egrid), dim3(kBlock), 0,
-                       stream, a->row_ptr, static_cast<const float*>(a->vals),
+                       stream, row_ptr, static_cast<const float*>(vals),
                        idx_in, n, nnz, d_t_col_idx, static_cast<float*>(d_t_vals));
   if (check_launch("tr_gather"))
     return -1;
@@ -264,15 +298,13 @@ csr_transpose(const CsrHandle* a, int64_t* d_t_row_ptr, int32_t* d_t_col_idx,
   ST_CHECK(hipMemsetAsync(d_order, 0, sizeof(uint32_t) * (size_t)n, stream));
   if (launch_csr_plan(d_t_row_ptr, n, d_pcnt, d_cf, d_order, stream))
     return -1;
-  uint32_t cf[csr::kClasses + 1];
-  ST_CHECK(hipMemcpyAsync(cf, d_cf, sizeof(cf), hipMemcpyDeviceToHost, stream));
+  ST_CHECK(hipMemcpyAsync(cf, d_cf, sizeof(uint32_t) * (csr::kClasses + 1),
+                          hipMemcpyDeviceToHost, stream));
   ST_CHECK(hipStreamSynchronize(stream));
-  CsrHandle* h = nullptr;
-  if (csr_make_handle(a->dtype, n, nnz, d_t_row_ptr, d_t_col_idx, d_t_vals,
-                      d_order, cf, &h, empty_rows, first_empty))
-    return -1;
-  order.p = nullptr; // the handle's now
-  *out = h;
+  order.p = nullptr; // the caller's now
+  *d_order_out = d_order;
+  *empty_rows_out = empty_rows;
+  *first_empty_out = first_empty;
   return 0;
 }
 

@@ -174,8 +174,77 @@ struct CsrTermsHandle
   const CsrHandle* csr; // the matrix it was checked against
   const void* u[4];
   const void* w[4];
+  // st_csr_pattern_terms_create: the pattern handle it was checked against
+  // (csr is null then, so every values call refuses the object)
+  const struct CsrPatternHandle* pattern;
 };
 constexpr uint32_t kCsrTermsMagic = 0x43535454u;
+// the pattern-only operator diag(r) P diag(c) (st_csr_pattern.hip): validated
+// row_ptr / col_idx with their plan, no values at all.  A kind of its own:
+// as_csr refuses it by its magic, as_csr_pattern refuses a CsrHandle.  The
+// two arrays and the scales (either may be null = all ones) stay the caller's.
+struct CsrPatternHandle
+{
+  uint32_t magic; // kCsrPatternMagic while alive
+  int dtype;      // 0 = f32, 1 = f64: the scales' and the vectors'
+  int device;
+  uint32_t n;
+  uint64_t nnz;
+  const int64_t* row_ptr;
+  const int32_t* col_idx;
+  const void* row_scale; // [n] or null
+  const void* col_scale; // [n] or null
+  uint32_t* d_order;     // [n] row indices sorted by class
+  uint32_t row_first[5];
+  uint32_t blk_first[5];
+  uint32_t empty_rows;
+  uint32_t first_empty;
+};
+constexpr uint32_t kCsrPatternMagic = 0x43535250u;
+const CsrPatternHandle* as_csr_pattern(const void* p, const char* what);
+// null + error unless t is a live terms object made for this pattern handle
+const CsrTermsHandle* as_csr_pattern_terms(const void* t, const CsrPatternHandle* p,
+                                           const char* what);
+int csr_pattern_refuse_empty(const CsrPatternHandle* p, const char* what);
+// validates as csr_create (row_ptr, col_idx, the plan), then the scales in one
+// device pass (row_scale before col_scale, the lowest index); synchronises
+int csr_pattern_create(int dtype, uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
+                       const int32_t* d_col_idx, const void* d_row_scale,
+                       const void* d_col_scale, hipStream_t stream,
+                       CsrPatternHandle** out, uint32_t flags = 0);
+int csr_pattern_destroy(CsrPatternHandle* p);
+// T(P) into the caller's two arrays, the scales swapped; synchronises
+int csr_pattern_transpose(const CsrPatternHandle* p, int64_t* d_t_row_ptr,
+                          int32_t* d_t_col_idx, hipStream_t stream,
+                          CsrPatternHandle** out, uint32_t flags = 0);
+// csr_terms_create's contract on the pattern operator (the vectors, launch 0,
+// the rows); synchronises
+int csr_pattern_terms_create(const CsrPatternHandle* p, uint32_t K,
+                             const void* const* d_u, const void* const* d_w,
+                             hipStream_t stream, CsrTermsHandle** out);
+// scratch: dots | partial (csr_terms_dots_bytes(K), unused when t is null);
+// z [n] apart
+int launch_csr_pattern_rowsum(const CsrPatternHandle* p, const CsrTermsHandle* t,
+                              void* s, void* dots_part, hipStream_t stream);
+int launch_csr_pattern_round(const CsrPatternHandle* p, const CsrTermsHandle* t,
+                             const void* s_prev, void* s_next, const void* v_prev,
+                             void* v_cur, void* z, void* dots_part, double eps,
+                             uint32_t k, uint32_t max_itr, uint32_t semantics,
+                             st_state* st, hipStream_t stream);
+// the two checked passes and the plan that csr_create and csr_pattern_create
+// share: row_ptr on its own, the columns only after it passed, then the plan.
+// *d_order_out [n] is the caller's to free or to hand to a handle; cf [5]
+int csr_check_and_plan(uint32_t n, uint64_t nnz, const int64_t* d_row_ptr,
+                       const int32_t* d_col_idx, hipStream_t stream, bool empty_ok,
+                       uint32_t** d_order_out, uint32_t* cf, uint32_t* empty_rows,
+                       uint32_t* first_empty);
+// the stable sort by column that csr_transpose and csr_pattern_transpose
+// share: vals / d_t_vals null = source rows only.  Outputs as above
+int csr_transpose_arrays(int dtype, uint32_t n, uint64_t nnz, const int64_t* row_ptr,
+                         const int32_t* col_idx, const void* vals,
+                         int64_t* d_t_row_ptr, int32_t* d_t_col_idx, void* d_t_vals,
+                         hipStream_t stream, uint32_t flags, uint32_t** d_order_out,
+                         uint32_t* cf, uint32_t* empty_rows, uint32_t* first_empty);
 int csr_refuse_empty(const CsrHandle* h, const char* what); // -1 + error if it has empty rows
 // validates u / w on the device (one pass), then s_0 of the operator;
 // synchronises `stream`

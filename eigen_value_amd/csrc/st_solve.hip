@@ -322,13 +322,16 @@ resolve(const st_options* opt, Resolved* r)
 // round, dots and partials in the flat scratch, unused here); with `csr_b`
 // the operator is the product csr_b * csr (st_csr_product.hip's K0 and
 // three-launch round, y in the second slot of the ring)
+// pat != nullptr (csr is null then): the pattern-only operator of that handle
+// (st_csr_pattern.hip's launch 0 and round, z where the CSR round keeps x,
+// `terms` a terms object of the pattern handle or null)
 template <typename T>
 int64_t
 solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
              T* eigen_val, uint32_t* iter_cnt, const st_options* opt,
              st_stats* stats, bool flush_matrix = true, int storage = 0,
              const CsrHandle* csr = nullptr, const CsrTermsHandle* terms = nullptr,
-             const CsrHandle* csr_b = nullptr)
+             const CsrHandle* csr_b = nullptr, const CsrPatternHandle* pat = nullptr)
 {
   static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value,
                 "fp32 / fp64 vectors");
@@ -362,7 +365,7 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
     if (ensure_trace(c, row_bytes * o.max_itr))
       return -1;
   }
-  const bool mfree = storage != 0 || csr || (o.flags & ST_FLAG_MATRIX_FREE) != 0;
+  const bool mfree = storage != 0 || csr || pat || (o.flags & ST_FLAG_MATRIX_FREE) != 0;
   // large matrices: the flat round (k_flat + k_parts)
   const bool flat = !mfree && round_flat_pays(n, n, sizeof(T));
   // the flat round stores the matrix every kDefer rounds (bit-identical
@@ -379,7 +382,7 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   }
   // K0 takes the flat form wherever the flat round pays (the matrix-free
   // loop's too)
-  const bool flat_k0 = storage == 0 && !csr && round_flat_pays(n, n, sizeof(T));
+  const bool flat_k0 = storage == 0 && !csr && !pat && round_flat_pays(n, n, sizeof(T));
   if (flat_k0 && ensure_part(c, sizeof(T) * round_flat_scratch(n, n)))
     return -1;
   if (terms && ensure_part(c, csr_terms_dots_bytes(terms->K)))
@@ -428,7 +431,10 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
     (void)hipEventRecord(ev[0], s);
   }
   T* const s0 = defer ? ring_s[0] : s_buf[0];
-  if (csr) { // K0 on the CSR matrix
+  if (pat) { // launch 0 on the pattern operator
+    if (launch_csr_pattern_rowsum(pat, terms, s0, d_part, s))
+      return -1;
+  } else if (csr) { // K0 on the CSR matrix
     if (csr_b    ? launch_csr_product_rowsum(csr_b, csr, s0, d_y, s)
         : terms ? launch_csr_terms_rowsum(csr, terms, s0, d_part, s)
                 : launch_csr_rowsum(csr, s0, s))
@@ -471,7 +477,12 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
         ev.push_back(eb);
         (void)hipEventRecord(ea, s);
       }
-      if (csr && csr_b) // launch k+1 evaluates round k
+      if (pat) // launch k+1 evaluates round k
+        rc |= launch_csr_pattern_round(pat, terms, s_buf[cur], s_buf[cur ^ 1],
+                                       vb[k & 1], vb[(k + 1) & 1], ring_s[0], d_part,
+                                       o.eps, k + 1, o.max_itr, o.semantics,
+                                       c->d_state, s);
+      else if (csr && csr_b) // launch k+1 evaluates round k
         rc |= launch_csr_product_round(csr_b, csr, s_buf[cur], s_buf[cur ^ 1],
                                        vb[k & 1], vb[(k + 1) & 1], ring_s[0],
                                        d_y, o.eps, k + 1, o.max_itr,
@@ -698,6 +709,185 @@ solve_csr(Context* c, const CsrHandle* h, void* d_v_out, void* v_host,
                              static_cast<float*>(v_host),
                              static_cast<float*>(eigen_val), iter_cnt, opt,
                              stats, false, 0, h, terms);
+}
+
+// The solve on a validated pattern handle (st_csr_pattern_create): solve_csr
+// with the pattern launchers.  Everything is checked before anything is
+// enqueued.
+int64_t
+solve_csr_pattern(Context* c, const CsrPatternHandle* h, void* d_v_out, void* v_host,
+                  void* eigen_val, uint32_t* iter_cnt, const st_options* opt,
+                  st_stats* stats, const CsrTermsHandle* terms = nullptr)
+{
+  if (csr_check_flags(opt))
+    return -1;
+  if (!terms && csr_pattern_refuse_empty(h, "st_solve_csr_pattern"))
+    return -1;
+  ST_REQUIRE(c, "null queue");
+  ST_REQUIRE(c->device == h->device,
+             "csr pattern solve: the pattern lives on device %d, the queue on %d",
+             h->device, c->device);
+  // never dereferenced: solve_device reads the pattern through the handle
+  void* tag = const_cast<CsrPatternHandle*>(h);
+  if (h->dtype)
+    return solve_device<double>(c, static_cast<double*>(tag), h->n,
+                                static_cast<double*>(d_v_out),
+                                static_cast<double*>(v_host),
+                                static_cast<double*>(eigen_val), iter_cnt, opt,
+                                stats, false, 0, nullptr, terms, nullptr, h);
+  return solve_device<float>(c, static_cast<float*>(tag), h->n,
+                             static_cast<float*>(d_v_out),
+                             static_cast<float*>(v_host),
+                             static_cast<float*>(eigen_val), iter_cnt, opt,
+                             stats, false, 0, nullptr, terms, nullptr, h);
+}
+
+// The host-pointer solve of diag(r) P diag(c) + sum_j u_j w_j^T: everything
+// validated on the host first (dtype, opt's flags, flags, n, row_ptr, the
+// columns, the scales row before column, K, the vectors, then the rows of the
+// operator or - without terms - the empty rows); the workspace holds
+// [row_ptr | col_idx | r | c | u_0 | w_0 | u_1 | ...]
+template <typename T>
+int
+check_pattern_host_t(uint32_t n, const int64_t* row_ptr, const int32_t* col_idx,
+                     const void* r, const void* c, uint32_t K, const void* const* u,
+                     const void* const* w, bool scales_only)
+{
+  char msg[384];
+  if (scales_only) {
+    if (csr::check_pattern_scales<T>(n, static_cast<const T*>(r),
+                                     static_cast<const T*>(c), msg, sizeof(msg))) {
+      set_error("%s", msg);
+      return -1;
+    }
+    return 0;
+  }
+  const T* uu[csr::kTermsMax] = {};
+  const T* ww[csr::kTermsMax] = {};
+  for (uint32_t j = 0; j < K; j++) {
+    uu[j] = static_cast<const T*>(u[j]);
+    ww[j] = static_cast<const T*>(w[j]);
+  }
+  if (csr::check_terms_vectors<T>(n, K, uu, ww, msg, sizeof(msg)) ||
+      csr::check_pattern_terms_rows<T>(n, row_ptr, col_idx, static_cast<const T*>(r),
+                                       static_cast<const T*>(c), K, uu, ww, msg,
+                                       sizeof(msg))) {
+    set_error("%s", msg);
+    return -1;
+  }
+  return 0;
+}
+
+int64_t
+solve_host_csr_pattern(Context* c, int dtype, uint32_t n, uint64_t nnz,
+                       const int64_t* row_ptr, const int32_t* col_idx,
+                       const void* row_scale, const void* col_scale, uint32_t K,
+                       const void* const* u, const void* const* w, uint32_t flags,
+                       void* eigen_val, void* eigen_vec, uint32_t* iter_cnt,
+                       const st_options* opt, st_stats* stats)
+{
+  ST_REQUIRE(dtype == 0 || dtype == 1,
+             "csr: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  if (csr_check_flags(opt))
+    return -1;
+  ST_REQUIRE((flags & ~csr::kEmptyRowsOk) == 0,
+             "max_eigen_value_csr_pattern_ex: unknown flags %u", flags);
+  {
+    char msg[384];
+    if (csr::check_pattern_host(dtype, n, nnz, row_ptr, col_idx, msg, sizeof(msg),
+                                (flags & csr::kEmptyRowsOk) != 0)) {
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  if (dtype ? check_pattern_host_t<double>(n, row_ptr, col_idx, row_scale, col_scale, 0,
+                                           nullptr, nullptr, true)
+            : check_pattern_host_t<float>(n, row_ptr, col_idx, row_scale, col_scale, 0,
+                                          nullptr, nullptr, true))
+    return -1;
+  {
+    char msg[384];
+    if (csr::check_pattern_terms_count(K, msg, sizeof(msg))) {
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  if (K) {
+    ST_REQUIRE(u && w, "csr terms: null vector table");
+    if (dtype ? check_pattern_host_t<double>(n, row_ptr, col_idx, row_scale, col_scale,
+                                             K, u, w, false)
+              : check_pattern_host_t<float>(n, row_ptr, col_idx, row_scale, col_scale, K,
+                                            u, w, false))
+      return -1;
+  } else {
+    uint32_t lowest = n;
+    const uint32_t empty = csr::count_empty_rows(row_ptr, n, &lowest);
+    if (empty) {
+      char msg[384];
+      csr::describe_pattern_needs_terms("max_eigen_value_csr_pattern_ex", lowest, empty,
+                                        msg, sizeof(msg));
+      set_error("%s", msg);
+      return -1;
+    }
+  }
+  ST_REQUIRE(eigen_val && eigen_vec && iter_cnt, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  const size_t elem = dtype ? 8 : 4;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_col = up(4 * nnz),
+               b_vec = up(elem * (size_t)n);
+  if (ensure_matrix(c, b_ptr + b_col + (2 + 2 * (size_t)K) * b_vec))
+    return -1;
+  char* base = static_cast<char*>(c->d_mat);
+  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
+  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr);
+  char* vec0 = base + b_ptr + b_col;
+  void* d_rs = row_scale ? vec0 : nullptr;
+  void* d_cs = col_scale ? vec0 + b_vec : nullptr;
+  const void* d_u[csr::kTermsMax] = {};
+  const void* d_w[csr::kTermsMax] = {};
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1), hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice, c->stream));
+  if (d_rs)
+    ST_CHECK(hipMemcpyAsync(d_rs, row_scale, elem * (size_t)n, hipMemcpyHostToDevice,
+                            c->stream));
+  if (d_cs)
+    ST_CHECK(hipMemcpyAsync(d_cs, col_scale, elem * (size_t)n, hipMemcpyHostToDevice,
+                            c->stream));
+  for (uint32_t j = 0; j < K; j++) {
+    char* at = vec0 + (2 + 2 * (size_t)j) * b_vec;
+    ST_CHECK(hipMemcpyAsync(at, u[j], elem * (size_t)n, hipMemcpyHostToDevice,
+                            c->stream));
+    ST_CHECK(hipMemcpyAsync(at + b_vec, w[j], elem * (size_t)n, hipMemcpyHostToDevice,
+                            c->stream));
+    d_u[j] = at;
+    d_w[j] = at + b_vec;
+  }
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  CsrPatternHandle* h = nullptr;
+  if (csr_pattern_create(dtype, n, nnz, d_ptr, d_col, d_rs, d_cs, c->stream, &h, flags))
+    return -1;
+  CsrTermsHandle* t = nullptr;
+  if (K && csr_pattern_terms_create(h, K, d_u, d_w, c->stream, &t)) {
+    (void)csr_pattern_destroy(h);
+    return -1;
+  }
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  const int64_t rc =
+    solve_csr_pattern(c, h, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local, t);
+  (void)csr_terms_destroy(t);
+  (void)csr_pattern_destroy(h);
+  if (rc < 0)
+    return -1;
+  local.h2d_ms = h2d;
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
 }
 
 // The host-pointer solve of A + sum_j u_j w_j^T: everything validated on the
@@ -2148,6 +2338,63 @@ csr_transpose_on(Context* c, const CsrHandle* a, int64_t* d_t_row_ptr,
 }
 
 int
+csr_pattern_create_on(Context* c, int dtype, uint32_t n, uint64_t nnz,
+                      const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                      const void* d_row_scale, const void* d_col_scale, void** out,
+                      uint32_t flags)
+{
+  ST_REQUIRE(out, "st_csr_pattern_create: null output pointer");
+  *out = nullptr;
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  CsrPatternHandle* h = nullptr;
+  if (csr_pattern_create(dtype, n, nnz, d_row_ptr, d_col_idx, d_row_scale, d_col_scale,
+                         c->stream, &h, flags))
+    return -1;
+  *out = h;
+  return 0;
+}
+
+int
+csr_pattern_transpose_on(Context* c, const CsrPatternHandle* p, int64_t* d_t_row_ptr,
+                         int32_t* d_t_col_idx, void** out, uint32_t flags)
+{
+  ST_REQUIRE(out, "st_csr_pattern_transpose: null output pointer");
+  *out = nullptr;
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  ST_REQUIRE(c->device == p->device,
+             "csr transpose: the matrix lives on device %d, the queue on %d",
+             p->device, c->device);
+  CsrPatternHandle* h = nullptr;
+  if (csr_pattern_transpose(p, d_t_row_ptr, d_t_col_idx, c->stream, &h, flags))
+    return -1;
+  *out = h;
+  return 0;
+}
+
+int
+csr_pattern_terms_create_on(Context* c, const CsrPatternHandle* h, uint32_t K,
+                            const void* const* d_u, const void* const* d_w, void** out)
+{
+  ST_REQUIRE(out, "st_csr_pattern_terms_create: null output pointer");
+  *out = nullptr;
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  ST_REQUIRE(c->device == h->device,
+             "csr terms: the matrix lives on device %d, the queue on %d",
+             h->device, c->device);
+  CsrTermsHandle* t = nullptr;
+  if (csr_pattern_terms_create(h, K, d_u, d_w, c->stream, &t))
+    return -1;
+  *out = t;
+  return 0;
+}
+
+int
 csr_batch_create_on(Context* c, int dtype, uint32_t batch,
                     const uint32_t* mat_first, uint64_t nnz,
                     const int64_t* d_row_ptr, const int32_t* d_col_idx,
@@ -2614,6 +2861,80 @@ max_eigen_value_csr_left_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
   st::DeviceGuard guard;
   return st::solve_host_csr_left(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
                                  vals, eigen_val, eigen_vec, iter_cnt, opt, stats);
+}
+
+int
+st_csr_pattern_create(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                      const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                      const void* d_row_scale, const void* d_col_scale,
+                      unsigned int flags, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::csr_pattern_create_on(st::as_ctx(wq), dtype, n, nnz, d_row_ptr, d_col_idx,
+                                   d_row_scale, d_col_scale, out, flags);
+}
+
+int
+st_csr_pattern_transpose(void* wq, void* pat, int64_t* d_t_row_ptr,
+                         int32_t* d_t_col_idx, unsigned int flags, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (out)
+    *out = nullptr;
+  const st::CsrPatternHandle* p = st::as_csr_pattern(pat, "st_csr_pattern_transpose");
+  if (!p)
+    return -1;
+  return st::csr_pattern_transpose_on(st::as_ctx(wq), p, d_t_row_ptr, d_t_col_idx, out,
+                                      flags);
+}
+
+int
+st_csr_pattern_terms_create(void* wq, void* pat, uint32_t K, const void* const* d_u,
+                            const void* const* d_w, void** out)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (out)
+    *out = nullptr;
+  const st::CsrPatternHandle* h = st::as_csr_pattern(pat, "st_csr_pattern_terms_create");
+  if (!h)
+    return -1;
+  return st::csr_pattern_terms_create_on(st::as_ctx(wq), h, K, d_u, d_w, out);
+}
+
+int64_t
+st_solve_csr_pattern(void* wq, void* pat, void* terms, void* d_eigen_vec,
+                     void* eigen_vec_host, void* eigen_val, unsigned int* iter_cnt,
+                     const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  const st::CsrPatternHandle* h = st::as_csr_pattern(pat, "st_solve_csr_pattern");
+  if (!h)
+    return -1;
+  const st::CsrTermsHandle* t = nullptr;
+  if (terms && !(t = st::as_csr_pattern_terms(terms, h, "st_solve_csr_pattern")))
+    return -1;
+  return st::solve_csr_pattern(st::as_ctx(wq), h, d_eigen_vec, eigen_vec_host, eigen_val,
+                               iter_cnt, opt, stats, t);
+}
+
+int64_t
+max_eigen_value_csr_pattern_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                               const int64_t* row_ptr, const int32_t* col_idx,
+                               const void* row_scale, const void* col_scale, uint32_t K,
+                               const void* const* u, const void* const* w,
+                               unsigned int flags, void* eigen_val, void* eigen_vec,
+                               unsigned int* iter_cnt, const st_options* opt,
+                               st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_host_csr_pattern(st::as_ctx(wq), dtype, n, nnz, row_ptr, col_idx,
+                                    row_scale, col_scale, K, u, w, flags, eigen_val,
+                                    eigen_vec, iter_cnt, opt, stats);
 }
 
 int64_t

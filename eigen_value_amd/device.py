@@ -405,6 +405,166 @@ class CsrMatrix:
             pass
 
 
+class CsrPattern:
+    """The pattern-only operator ``diag(row_scale) · P · diag(col_scale)`` of
+    an unweighted graph on the device (``st_csr_pattern_create``): int64
+    ``crow_indices`` [n + 1] and int32 ``col_indices`` [nnz] - no values at
+    all; ``P[i][j]`` is the number of entries of row i with column j.  The
+    scales are optional tensors [n], finite and strictly positive; None means
+    all ones and costs nothing.  A round reads nnz * 4 bytes of matrix.
+
+    ``dtype`` is the scales' (they must agree); without scales it is
+    ``torch.float32`` unless given.  Built from ``(crow_indices, col_indices,
+    n)`` - device tensors, index dtypes converted as needed - or from a
+    ``torch.sparse_csr`` tensor, whose values are ignored.  Raises
+    ``EigenValueError`` naming the first offending row, entry or scale.
+
+    ``transpose()`` gives T(P) with the scales swapped
+    (``st_csr_pattern_transpose``); ``.T`` is the same, built once, kept, and
+    closed with this object.  ``allow_empty_rows`` as ``CsrMatrix``: such a
+    pattern is solved with ``CsrTerms`` (``solve_csr_pattern(p, terms)``,
+    ``pagerank``).  Not accepted by the product operator, ``hits``, the
+    multi-column and batched solves and ``csr_apply``: those take a
+    ``CsrMatrix`` (with values of 1)."""
+
+    _t = None
+    allow_empty_rows = False
+    empty_rows = 0
+
+    def __init__(self, crow_indices, col_indices=None, n: Optional[int] = None, *,
+                 row_scale=None, col_scale=None, allow_empty_rows: bool = False,
+                 solver: Optional["DeviceSolver"] = None, dtype=None):
+        if not isinstance(allow_empty_rows, bool):
+            raise TypeError("allow_empty_rows must be a bool, got "
+                            f"{type(allow_empty_rows).__name__}")
+        torch = _torch()
+        self.handle = ctypes.c_void_p()
+        self.L = _lib.load()
+        if col_indices is None:
+            sp = crow_indices
+            if sp.layout != torch.sparse_csr:
+                raise TypeError(f"a torch.sparse_csr tensor required, got layout {sp.layout}")
+            assert sp.dim() == 2 and sp.shape[0] == sp.shape[1], "must be square"
+            n = sp.shape[0]
+            crow_indices, col_indices = sp.crow_indices(), sp.col_indices()
+        _check_cuda(crow_indices, col_indices, row_scale, col_scale)
+        for name, x in (("row_scale", row_scale), ("col_scale", col_scale)):
+            if x is None:
+                continue
+            if not isinstance(x, torch.Tensor):
+                raise TypeError(f"{name} must be a torch tensor, got {type(x).__name__}")
+            _sfx(x)
+            if dtype is not None and x.dtype != dtype:
+                raise TypeError(f"{name} is {x.dtype}, dtype {dtype}")
+            dtype = x.dtype
+        self.dtype = torch.float32 if dtype is None else dtype
+        if self.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"float32/float64 required, got {self.dtype}")
+        self.dtype_code = 1 if self.dtype == torch.float64 else 0
+        self.n = int(crow_indices.numel() - 1 if n is None else n)
+        if crow_indices.numel() != self.n + 1:
+            raise ValueError(f"crow_indices has {crow_indices.numel()} elements, n + 1 = "
+                             f"{self.n + 1} required")
+        self.crow = crow_indices.to(torch.int64).contiguous()
+        self.col = col_indices.to(torch.int32).contiguous()
+        self.nnz = int(col_indices.numel())
+        self.device = self.crow.device
+        for name, x in (("row_scale", row_scale), ("col_scale", col_scale)):
+            if x is not None and (tuple(x.shape) != (self.n,) or x.device != self.device):
+                raise ValueError(f"{name} must be a tensor of shape ({self.n},) on "
+                                 f"{self.device}")
+        self.row_scale = None if row_scale is None else row_scale.contiguous()
+        self.col_scale = None if col_scale is None else col_scale.contiguous()
+        own = solver is None
+        solver = solver or DeviceSolver(self.device)
+        try:
+            _lib.check(self.L.st_set_stream(solver.q, _stream(self.device)), "st_set_stream")
+            _lib.check(self.L.st_csr_pattern_create(
+                solver.q, self.dtype_code, self.n, self.nnz, _ptr(self.crow), _ptr(self.col),
+                _ptr(self.row_scale), _ptr(self.col_scale),
+                _lib.ST_CSR_EMPTY_ROWS_OK if allow_empty_rows else 0,
+                ctypes.byref(self.handle)), "st_csr_pattern_create")
+        finally:
+            if own:
+                solver.close()
+        self.allow_empty_rows = allow_empty_rows
+        self._read_empty()
+
+    def _read_empty(self) -> None:
+        k, lo = ctypes.c_uint32(), ctypes.c_uint32()
+        _lib.check(self.L.st_csr_pattern_empty_rows(self.handle, ctypes.byref(k),
+                                                    ctypes.byref(lo)),
+                   "st_csr_pattern_empty_rows")
+        self.empty_rows, self.first_empty = int(k.value), int(lo.value)
+
+    def plan(self):
+        """``(order, class_first)`` of the handle (``st_csr_pattern_get_plan``)."""
+        import numpy as np
+        order = np.zeros(self.n, dtype=np.uint32)
+        first = np.zeros(_lib.ST_CSR_CLASSES + 1, dtype=np.uint32)
+        _lib.check(self.L.st_csr_pattern_get_plan(self.handle, order.ctypes.data,
+                                                  first.ctypes.data),
+                   "st_csr_pattern_get_plan")
+        return order, first
+
+    def transpose(self, solver: Optional["DeviceSolver"] = None,
+                  allow_empty: bool = False) -> "CsrPattern":
+        """T(P) with the scales swapped (``st_csr_pattern_transpose``): the two
+        index arrays are byte for byte ``CsrMatrix.transpose``'s on the same
+        pattern.  Raises ``EigenValueError`` naming the lowest column without
+        an entry unless ``allow_empty``.  The result shares the scale tensors
+        and is otherwise independent of this object."""
+        if not isinstance(allow_empty, bool):
+            raise TypeError(f"allow_empty must be a bool, got {type(allow_empty).__name__}")
+        torch = _torch()
+        if not self.handle.value:
+            raise ValueError("the pattern is closed")
+        t = object.__new__(CsrPattern)
+        t.handle = ctypes.c_void_p()
+        t.L = self.L
+        t.dtype, t.dtype_code = self.dtype, self.dtype_code
+        t.n, t.nnz, t.device = self.n, self.nnz, self.device
+        t.row_scale, t.col_scale = self.col_scale, self.row_scale
+        t.crow = torch.empty(self.n + 1, dtype=torch.int64, device=self.device)
+        t.col = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
+        own = solver is None
+        solver = solver or DeviceSolver(self.device)
+        try:
+            _lib.check(self.L.st_set_stream(solver.q, _stream(self.device)), "st_set_stream")
+            _lib.check(self.L.st_csr_pattern_transpose(
+                solver.q, self.handle, _ptr(t.crow), _ptr(t.col),
+                _lib.ST_CSR_EMPTY_ROWS_OK if allow_empty else 0, ctypes.byref(t.handle)),
+                "st_csr_pattern_transpose")
+        finally:
+            if own:
+                solver.close()
+        t.allow_empty_rows = allow_empty
+        t._read_empty()
+        return t
+
+    @property
+    def T(self) -> "CsrPattern":
+        """``transpose()``, built at the first use and kept; closed with this
+        object."""
+        if self._t is None:
+            self._t = self.transpose()
+        return self._t
+
+    def close(self) -> None:
+        if self._t is not None:
+            self._t.close()
+            self._t = None
+        if self.handle is not None and self.handle.value:
+            self.L.st_csr_pattern_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def csr_transpose_host(indptr, indices, data, allow_empty: bool = False):
     """T(A) of host (numpy) CSR arrays by the library's host twin
     (``st_csr_transpose_host``; no GPU): ``(t_indptr, t_indices, t_data)``.
@@ -422,11 +582,13 @@ class CsrTerms:
     devices are checked here before any library call; the entries and the rows
     of ``M`` on the device (``EigenValueError`` naming the term, the vector
     and the index, or the row without a positive entry).  Bound to ``csr``:
-    every call refuses it with another matrix."""
+    every call refuses it with another matrix.  ``csr`` may be a
+    ``CsrPattern`` (``st_csr_pattern_terms_create``): the terms then serve
+    ``solve_csr_pattern`` and the ``csr_pattern_*`` steps."""
 
-    def __init__(self, csr: CsrMatrix, u, w, *, solver: Optional["DeviceSolver"] = None):
+    def __init__(self, csr, u, w, *, solver: Optional["DeviceSolver"] = None):
         torch = _torch()
-        if not isinstance(csr, CsrMatrix):
+        if not isinstance(csr, (CsrMatrix, CsrPattern)):
             raise TypeError(f"a CsrMatrix required, got {type(csr).__name__}")
         if not csr.handle.value:
             raise ValueError("the matrix is closed")
@@ -453,9 +615,14 @@ class CsrTerms:
         solver = solver or DeviceSolver(csr.device)
         try:
             _lib.check(self.L.st_set_stream(solver.q, _stream(csr.device)), "st_set_stream")
-            _lib.check(self.L.st_csr_terms_create(solver.q, csr.handle, self.K, pu, pw,
-                                                  ctypes.byref(self.handle)),
-                       "st_csr_terms_create")
+            if isinstance(csr, CsrPattern):
+                _lib.check(self.L.st_csr_pattern_terms_create(
+                    solver.q, csr.handle, self.K, pu, pw, ctypes.byref(self.handle)),
+                    "st_csr_pattern_terms_create")
+            else:
+                _lib.check(self.L.st_csr_terms_create(solver.q, csr.handle, self.K, pu, pw,
+                                                      ctypes.byref(self.handle)),
+                           "st_csr_terms_create")
         finally:
             if own:
                 solver.close()
@@ -523,6 +690,78 @@ def csr_terms_round(csr: CsrMatrix, terms: CsrTerms, s_prev, s_next, v_prev, v_c
         csr.handle, terms.handle, _ptr(s_prev), _ptr(s_next), _ptr(v_prev), _ptr(v_cur),
         _ptr(scratch), float(eps), k, max_itr, semantics, _ptr(state), _stream(csr.device)),
         "csr_terms_round")
+
+
+def _check_pattern(pat, name: str = "pat") -> None:
+    if not isinstance(pat, CsrPattern):
+        raise TypeError(f"{name}: a CsrPattern required, got {type(pat).__name__}")
+    if not pat.handle.value:
+        raise ValueError(f"{name}: the pattern is closed")
+
+
+def _check_pattern_terms(pat, terms) -> None:
+    if terms is not None:
+        if not isinstance(terms, CsrTerms):
+            raise TypeError(f"terms must be a CsrTerms, got {type(terms).__name__}")
+        if terms.csr is not pat:
+            raise ValueError("terms were made for another matrix")
+
+
+def csr_pattern_scratch(pat: CsrPattern, terms: Optional[CsrTerms] = None):
+    """A fresh scratch tensor for ``csr_pattern_rowsum`` / ``csr_pattern_round``
+    (``st_csr_pattern_scratch_bytes(n, K)``, K = 0 without terms): dots and
+    partials first (``terms.dots(scratch)``), then z (``csr_pattern_z``)."""
+    torch = _torch()
+    _check_pattern(pat)
+    K = 0 if terms is None else terms.K
+    nbytes = int(pat.L.st_csr_pattern_scratch_bytes(pat.n, K))
+    return torch.zeros(nbytes, dtype=torch.uint8, device=pat.device)
+
+
+def csr_pattern_z(pat: CsrPattern, scratch, terms: Optional[CsrTerms] = None):
+    """z = col_scale * x as the last ``csr_pattern_round`` left it (x itself
+    without a column scale)."""
+    K = 0 if terms is None else terms.K
+    off = 256 + K * 2048 * 8
+    es = 8 if pat.dtype_code else 4
+    return scratch[off:off + pat.n * es].view(pat.dtype).clone()
+
+
+def csr_pattern_rowsum(pat: CsrPattern, terms: Optional[CsrTerms] = None, scratch=None,
+                       out=None):
+    """s_0 = row_scale * (P col_scale), plus the terms (``st_csr_pattern_rowsum``):
+    launch 0 of the pattern scheme.  ``scratch`` is needed with terms only."""
+    torch = _torch()
+    _check_pattern(pat)
+    _check_pattern_terms(pat, terms)
+    if out is None:
+        out = torch.empty(pat.n, dtype=pat.dtype, device=pat.device)
+    if scratch is None and terms is not None:
+        scratch = csr_pattern_scratch(pat, terms)
+    _check_cuda(out, scratch)
+    assert out.dtype == pat.dtype and out.numel() >= pat.n
+    _lib.check(_lib.load().st_csr_pattern_rowsum(
+        pat.handle, None if terms is None else terms.handle, _ptr(out), _ptr(scratch),
+        _stream(pat.device)), "csr_pattern_rowsum")
+    return out
+
+
+def csr_pattern_round(pat: CsrPattern, terms: Optional[CsrTerms], s_prev, s_next, v_prev,
+                      v_cur, scratch, state, *, eps: float = 1e-3, k: int = 1,
+                      max_itr: int = _lib.ST_MAX_ITR,
+                      semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Launch k >= 1 on the pattern operator (``st_csr_pattern_round``):
+    ``csr_mfree_round``'s contract (``csr_terms_round``'s with terms); a no-op
+    once the state's ``end`` is set and below k."""
+    _check_pattern(pat)
+    _check_pattern_terms(pat, terms)
+    _check_cuda(s_prev, s_next, v_prev, v_cur, scratch, state)
+    assert all(t.dtype == pat.dtype and t.numel() >= pat.n and t.is_contiguous()
+               for t in (s_prev, s_next, v_prev, v_cur))
+    _lib.check(_lib.load().st_csr_pattern_round(
+        pat.handle, None if terms is None else terms.handle, _ptr(s_prev), _ptr(s_next),
+        _ptr(v_prev), _ptr(v_cur), _ptr(scratch), float(eps), k, max_itr, semantics,
+        _ptr(state), _stream(pat.device)), "csr_pattern_round")
 
 
 class CsrMultiTerms:
@@ -1276,6 +1515,102 @@ class DeviceSolver:
         _lib.check(rc, "st_solve_csr")
         return float(ev.value), v, int(it.value), stats.as_dict()
 
+    def solve_csr_pattern(self, pat: "CsrPattern", terms: Optional["CsrTerms"] = None, *,
+                          left: bool = False, eps: Optional[float] = None,
+                          max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
+                          batch: int = 0, trace: bool = False,
+                          time_kernels: bool = False):
+        """The matrix-free solve of a ``CsrPattern`` (``st_solve_csr_pattern``):
+        nnz * 4 bytes of matrix per round.  Options and the return value are
+        ``solve_csr``'s.  ``terms``: a ``CsrTerms`` made for ``pat``.
+        ``left=True`` solves ``pat.T`` (scales swapped; made on the device at
+        the first use and kept); with terms the pattern is transposed with
+        ``allow_empty=True`` and the term vectors swap roles, kept with the
+        terms object."""
+        if not isinstance(left, bool):
+            raise TypeError(f"left must be a bool, got {type(left).__name__}")
+        torch = _torch()
+        if not isinstance(pat, CsrPattern):
+            raise TypeError(f"a CsrPattern required, got {type(pat).__name__} "
+                            "(solve_csr takes a CsrMatrix)")
+        _check_pattern_terms(pat, terms)
+        if pat.device.index != (self.device.index if self.device.index is not None
+                                else torch.cuda.current_device()):
+            raise ValueError(f"pattern on {pat.device}, solver context on {self.device}")
+        opts = dict(eps=eps, max_itr=max_itr, semantics=semantics, batch=batch,
+                    trace=trace, time_kernels=time_kernels)
+        if left and terms is not None:
+            if terms._left is None:
+                at = pat.transpose(self, allow_empty=True)
+                terms._left = (CsrTerms(at, terms.w, terms.u, solver=self), at)
+            tt, at = terms._left
+            return self.solve_csr_pattern(at, tt, **opts)
+        if left:
+            if pat._t is None:
+                pat._t = pat.transpose(self)
+            return self.solve_csr_pattern(pat.T, **opts)
+        v = torch.empty(pat.n, dtype=pat.dtype, device=pat.device)
+        ev = (ctypes.c_double if pat.dtype_code else ctypes.c_float)()
+        it = ctypes.c_uint32()
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace else 0))
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
+        stats = _lib.st_stats()
+        self._trace = (pat.n, pat.dtype)
+        _lib.check(self.L.st_set_stream(self.q, _stream(pat.device)), "st_set_stream")
+        rc = self.L.st_solve_csr_pattern(
+            self.q, pat.handle, None if terms is None else terms.handle, _ptr(v), None,
+            ctypes.byref(ev), ctypes.byref(it), ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(rc, "st_solve_csr_pattern")
+        return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def _pagerank_pattern(self, links: "CsrPattern", alpha: float, teleport, dangling,
+                          solve_options):
+        """``pagerank`` on a ``CsrPattern`` without scales: nothing of nnz
+        elements is allocated but the two transposed index arrays."""
+        torch = _torch()
+        if links.row_scale is not None or links.col_scale is not None:
+            raise ValueError("pagerank takes a CsrPattern without scales (the link "
+                             "weights are 1; it normalises the rows itself)")
+        if not links.handle.value:
+            raise ValueError("the pattern is closed")
+        n, dt, device = links.n, links.dtype, links.device
+
+        def dist(x, name):
+            if x is None:
+                return torch.full((n,), 1.0 / n, dtype=dt, device=device)
+            if not isinstance(x, torch.Tensor) or tuple(x.shape) != (n,):
+                raise ValueError(f"{name} must be a tensor of shape ({n},)")
+            x = x.to(device=device, dtype=dt)
+            return x / x.sum()
+
+        t = dist(teleport, "teleport")
+        outdeg = (links.crow[1:] - links.crow[:-1]).to(dt)   # 0 for a dangling node
+        empty = outdeg == 0
+        # column c of P^T is row c of P: alpha / outdeg, 1 where no entry reads it
+        scale = alpha / torch.where(empty, torch.full_like(outdeg, alpha), outdeg)
+        Lt = links.transpose(self, allow_empty=True)
+        Pt = CsrPattern(Lt.crow, Lt.col, n, col_scale=scale, allow_empty_rows=True,
+                        solver=self)
+        one = torch.ones(n, dtype=dt, device=device)
+        ind = empty.to(dt)
+        if dangling is None:
+            u, w = [t], [(1.0 - alpha) * one + alpha * ind]
+        else:
+            u, w = [t, dist(dangling, "dangling")], [(1.0 - alpha) * one, alpha * ind]
+        terms = None
+        try:
+            terms = CsrTerms(Pt, u, w, solver=self)
+            lam, v, it, stats = self.solve_csr_pattern(Pt, terms, **solve_options)
+        finally:
+            if terms is not None:
+                terms.close()
+            Pt.close()
+            Lt.close()
+        return v / v.sum(), lam, it, stats
+
     def pagerank(self, A: "CsrMatrix", alpha: float = 0.85, teleport=None, dangling=None,
                  **solve_options):
         """PageRank of a link graph, on the device throughout.  ``A`` is a
@@ -1292,16 +1627,24 @@ class DeviceSolver:
         ``solve_csr``'s (eps, max_itr, semantics, batch, trace,
         time_kernels).
 
+        ``A`` may also be a ``CsrPattern`` without scales (an unweighted
+        graph): the out-degrees come from ``crow``, the pattern is transposed,
+        ``col_scale = alpha / outdeg`` (1 where outdeg is 0: no entry reads
+        it) goes on the transposed handle and the same terms are solved with
+        ``solve_csr_pattern`` - no tensor of nnz values exists on that route.
+
         Returns ``(pi with sum 1, λ, iterations, stats)``; λ is 1 up to
         rounding."""
         torch = _torch()
-        if not isinstance(A, CsrMatrix):
+        if not isinstance(A, (CsrMatrix, CsrPattern)):
             raise TypeError(f"a CsrMatrix required, got {type(A).__name__}")
         alpha = float(alpha)
         if not 0.0 < alpha < 1.0:
             raise ValueError(f"alpha must be in (0, 1), got {alpha}")
         if "left" in solve_options or "terms" in solve_options:
             raise TypeError("pagerank builds its own terms and transposition")
+        if isinstance(A, CsrPattern):
+            return self._pagerank_pattern(A, alpha, teleport, dangling, solve_options)
         n, dt, device = A.n, A.dtype, A.device
 
         def dist(x, name):

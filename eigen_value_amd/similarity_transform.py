@@ -333,6 +333,129 @@ class EigenValue:
         _lib.check(ts, name, self.so_lib)
         return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
 
+    def similarity_transform_csr_pattern(self, indptr, indices=None, n: Optional[int] = None,
+                                         row_scale=None, col_scale=None, terms=None,
+                                         left: bool = False, *, dtype=None,
+                                         allow_empty_rows: bool = False,
+                                         eps: Optional[float] = None, max_itr: int = 0,
+                                         semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
+                                         time_kernels: bool = False,
+                                         trace_sums: bool = False):
+        """The matrix-free solve of the PATTERN-ONLY operator ``diag(row_scale)
+        · P · diag(col_scale)`` of an unweighted graph
+        (``max_eigen_value_csr_pattern_ex``): ``indptr`` [n + 1] and ``indices``
+        [nnz] as in ``scipy.sparse.csr_matrix``, ``P[i][j]`` the number of
+        entries of row i with column j; no value array is read or copied, and
+        the device reads nnz * 4 bytes of matrix per round.  A ``scipy.sparse``
+        matrix or a ``torch.sparse_csr`` tensor passed as the first argument
+        is accepted too: ITS VALUES ARE IGNORED, only its structure is used
+        (a float32 / float64 matrix sets the default ``dtype``).
+
+        ``row_scale`` / ``col_scale``: None (all ones) or arrays [n], finite
+        and strictly positive - 1 / outdeg as ``row_scale`` gives the
+        row-stochastic matrix, d^-1/2 twice the symmetric normalised one.
+        ``dtype`` (np.float32 / np.float64) is the vectors'; default: the
+        scales', the terms', the sparse matrix's, else float32.
+        ``terms=(u, w)`` adds ``sum_j u_j w_j^T`` as in
+        ``similarity_transform_csr``; ``allow_empty_rows`` (with terms only)
+        accepts rows without an entry.  ``left=True`` solves the transposed
+        operator: the pattern is transposed on the host, the scales swap, and
+        so do the term vectors.  Everything is validated on the host, the
+        error naming the row, the entry, the scale (``row_scale`` before
+        ``col_scale``) or the term.
+
+        Returns ``(λ, v, ts_ms, iterations)`` in ``dtype``."""
+        if not isinstance(left, bool):
+            raise TypeError(f"left must be a bool, got {type(left).__name__}")
+        if not isinstance(allow_empty_rows, bool):
+            raise TypeError("allow_empty_rows must be a bool, got "
+                            f"{type(allow_empty_rows).__name__}")
+        if terms is None and allow_empty_rows:
+            raise ValueError("allow_empty_rows needs terms: a row sum of the matrix alone "
+                             "would be divided by zero")
+        if terms is not None and (not isinstance(terms, (tuple, list)) or len(terms) != 2):
+            raise TypeError("terms must be a pair (u, w)")
+        sp_dtype = None
+        if indices is None:
+            sp = indptr
+            if hasattr(sp, "crow_indices"):          # a torch.sparse_csr tensor
+                assert sp.dim() == 2 and sp.shape[0] == sp.shape[1], "must be square !"
+                n = sp.shape[0]
+                sp_dtype = {"torch.float32": np.float32,
+                            "torch.float64": np.float64}.get(str(sp.dtype))
+                indptr, indices = (sp.crow_indices().cpu().numpy(),
+                                   sp.col_indices().cpu().numpy())
+            elif hasattr(sp, "tocsr"):               # any scipy.sparse matrix / array
+                sp = sp.tocsr()
+                assert sp.shape[0] == sp.shape[1], "must be square !"
+                n = sp.shape[0]
+                if sp.dtype in (np.float32, np.float64):
+                    sp_dtype = sp.dtype.type
+                indptr, indices = sp.indptr, sp.indices
+            else:
+                raise TypeError("indptr, indices arrays or a sparse matrix required, got "
+                                f"{type(sp).__name__}")
+        if dtype is None:
+            for x in (row_scale, col_scale) + (tuple(terms[0]) if terms is not None else ()):
+                if x is not None and getattr(x, "dtype", None) in (np.float32, np.float64):
+                    dtype = x.dtype
+                    break
+            else:
+                dtype = sp_dtype or np.float32
+        dt = np.dtype(dtype)
+        assert dt.num in (11, 12), "dtype must be float32 or float64 !"
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.asarray(indices)
+        assert indices.dtype.kind in "iu", "indices must be an integer array !"
+        if indices.size and (indices.min() < -2**31 or indices.max() >= 2**31):
+            raise _lib.EigenValueError("csr: a column index does not fit int32")
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        n = len(indptr) - 1 if n is None else int(n)
+        assert len(indptr) == n + 1, "indptr must have n + 1 elements !"
+
+        def scale(x, name):
+            if x is None:
+                return None
+            x = np.ascontiguousarray(x, dtype=dt)
+            if x.shape != (n,):
+                raise ValueError(f"{name} has shape {x.shape}, ({n},) required")
+            return x
+
+        row_scale, col_scale = scale(row_scale, "row_scale"), scale(col_scale, "col_scale")
+        K, u, w = 0, [], []
+        if terms is not None:
+            u, w = terms
+            K = _lib.check_terms_arg(u, w, n)
+            u = [np.ascontiguousarray(x, dtype=dt) for x in u]
+            w = [np.ascontiguousarray(x, dtype=dt) for x in w]
+        if left:
+            indptr, indices, _ = _lib.csr_transpose_host(
+                indptr, indices, np.ones(len(indices), dtype=np.float32), self.so_lib,
+                allow_empty=terms is not None)
+            row_scale, col_scale = col_scale, row_scale
+            u, w = w, u
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace_sums else 0))
+        self._trace = (n, dt)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
+        eigen_val = np.empty(1, dtype=dt)
+        eigen_vec = np.empty(n, dtype=dt)
+        iter_cnt = np.zeros(1, dtype=np.uint32)
+        pu = (ctypes.c_void_p * K)(*[x.ctypes.data for x in u]) if K else None
+        pw = (ctypes.c_void_p * K)(*[x.ctypes.data for x in w]) if K else None
+        ts = self.so_lib.max_eigen_value_csr_pattern_ex(
+            self.sycl_q, _lib.DTYPE_F32 if dt == np.float32 else _lib.DTYPE_F64, n,
+            len(indices), indptr.ctypes.data, indices.ctypes.data,
+            None if row_scale is None else row_scale.ctypes.data,
+            None if col_scale is None else col_scale.ctypes.data, K, pu, pw,
+            _lib.ST_CSR_EMPTY_ROWS_OK if (allow_empty_rows or (left and K)) else 0,
+            eigen_val.ctypes.data, eigen_vec.ctypes.data, iter_cnt.ctypes.data,
+            ctypes.byref(opt), None)
+        _lib.check(ts, "max_eigen_value_csr_pattern_ex", self.so_lib)
+        return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0])
+
     def similarity_transform_csr_multi(self, indptr, indices=None, data=None, *, terms=None,
                                        eps: Optional[float] = None, max_itr: int = 0,
                                        semantics: int = _lib.ST_SEM_SYCL, batch_rounds: int = 0,

@@ -907,6 +907,113 @@ int64_t max_eigen_value_csr_gram_ex(void* wq, int dtype, uint32_t n,
                                     const st_options* opt, st_stats* stats);
 
 /* ---------------------------------------------------------------------- */
+/* 3h. sparse (CSR) solve on a pattern-only matrix with row / column scales */
+/* ---------------------------------------------------------------------- */
+
+/* The operator M = diag(r) P diag(c) of an UNWEIGHTED graph: P[i][j] = the
+ * number of entries of row i with column j (row_ptr / col_idx as in 3c;
+ * duplicates count, as they add up there), r and c optional dense DEVICE
+ * vectors [n] in the handle's dtype, each finite and strictly positive; NULL
+ * means all ones and costs nothing at run time (the kernels are instantiated
+ * without it).  r = c = 1 is the adjacency matrix, r = 1 / outdeg the
+ * row-stochastic one, c = 1 / outdeg on the transposed pattern the
+ * column-stochastic P^T of PageRank, r = c = d^-1/2 the symmetric normalised
+ * one.  No value array exists: a round reads nnz * 4 bytes of matrix where
+ * st_solve_csr reads nnz * 8 (fp32) or nnz * 12 (fp64), and the device
+ * footprint of the matrix shrinks alike.  Launch k >= 1 is
+ *   x_i    = v_prev[i] * s_prev[i];  z_i = c[i] * x_i   (one rounding each;
+ *            only z is stored; max, stop test and state as k_csr_prep)
+ *   d_j    = w_j . x                j < K   (terms; on x, not on z)
+ *   tot_i  = the sum of z[col[e]] over row i in st_solve_csr's order: the same
+ *            lane classes, lane t on entries t, t + L, ..., the same tree;
+ *            a step is acc = acc + z, bit for bit fma(1, z, acc)
+ *   tot_i  = r[i] * tot_i           (one multiply, when r is given)
+ *   tot_i  = fma(u_j[i], d_j, tot_i)   j = 0 .. K-1
+ *   s_next = tot_i / (v_prev[i] * s_prev[i]);  v_cur as st_solve_csr
+ * and launch 0 the same sweep on z = c (or ones): s_0 = r * (P c).  Hence,
+ * bit for bit: without scales every result is st_solve_csr's (3c, 3e with
+ * terms) on the same arrays with vals = 1; with scales that are powers of two
+ * it is st_solve_csr's on vals[e] = r[row] * c[col] as long as nothing
+ * under- or overflows.  Other scales differ from that matrix by roundings (z
+ * is rounded once, the product r * c never formed).  A row's result depends
+ * on its own entries, its r and z only.
+ *
+ * A pattern handle is a kind of its own: every call of 3c - 3g refuses it
+ * ("not a CSR matrix handle"), and every call here refuses a st_csr_create
+ * handle ("not a CSR pattern handle").  Not offered on a pattern handle: the
+ * product operator and st_csr_apply (3g), the multi-column solve (3f), the
+ * batched solve (3d); build a st_csr_create handle with vals = 1 for those.
+ *
+ * st_csr_pattern_create: row_ptr and col_idx DEVICE arrays validated exactly
+ * as st_csr_create_ex validates them (same order, same messages; flags:
+ * ST_CSR_EMPTY_ROWS_OK or 0), then the plan, then ONE device pass over the
+ * scales that names the lowest offender, row_scale before col_scale:
+ * "csr pattern: row_scale[17] = -0.5 is not finite and positive".  The four
+ * arrays stay the caller's, read only, alive and unchanged until
+ * st_csr_pattern_destroy. */
+int st_csr_pattern_create(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                          const int64_t* d_row_ptr, const int32_t* d_col_idx,
+                          const void* d_row_scale, const void* d_col_scale,
+                          unsigned int flags, void** out);
+int st_csr_pattern_destroy(void* pat);
+/* As st_csr_get_plan / st_csr_empty_rows. */
+int st_csr_pattern_get_plan(void* pat, uint32_t* order_out, uint32_t* class_first);
+int st_csr_pattern_empty_rows(void* pat, uint32_t* count, uint32_t* lowest);
+/* T(P) into the caller's DEVICE arrays d_t_row_ptr [n + 1] and d_t_col_idx
+ * [nnz] (they must not overlap the source's or each other): st_csr_transpose's
+ * stable sort by column with a final gather of source rows only; both arrays
+ * are byte for byte st_csr_transpose_ex's on the same pattern with any values.
+ * The result is a pattern handle over them with r and c SWAPPED ((D_r P
+ * D_c)^T = D_c P^T D_r; the scale vectors are shared with the source handle).
+ * Same refusals: a column without an entry unless flags has
+ * ST_CSR_EMPTY_ROWS_OK, nnz >= 2^32, overlap. */
+int st_csr_pattern_transpose(void* wq, void* pat, int64_t* d_t_row_ptr,
+                             int32_t* d_t_col_idx, unsigned int flags, void** out);
+/* The terms of M + sum_j u_j w_j^T on a pattern handle: st_csr_terms_create's
+ * contract (1 <= K <= ST_CSR_TERMS_MAX; the vectors in one pass, then launch
+ * 0, then "row r of A + Σ u wᵀ has no positive entry").  The object is bound
+ * to this pattern handle - every call of 3e refuses it, and every call here
+ * one of another handle - and is destroyed with st_csr_terms_destroy. */
+int st_csr_pattern_terms_create(void* wq, void* pat, uint32_t K,
+                                const void* const* d_u, const void* const* d_w,
+                                void** out);
+/* The solve: st_solve_csr's conventions, flags, tracing and timing, through
+ * the same loop; `terms` a st_csr_pattern_terms_create object of `pat` or
+ * NULL.  An empty-rows handle without terms is refused, the lowest row named.
+ * Returns loop ms or negative. */
+int64_t st_solve_csr_pattern(void* wq, void* pat, void* terms, void* d_eigen_vec,
+                             void* eigen_vec_host, void* eigen_val,
+                             unsigned int* iter_cnt, const st_options* opt,
+                             st_stats* stats);
+/* Bytes of the scratch of st_csr_pattern_rowsum / st_csr_pattern_round:
+ * st_csr_terms_scratch_bytes' layout (dots [K] | partial [K][2048] | a vector
+ * [n]) with z where x stands; K = 0 is allowed (256 bytes, then z).  0 for a
+ * bad n or K.  No GPU needed. */
+uint64_t st_csr_pattern_scratch_bytes(uint32_t n, uint32_t K);
+/* The launch shape of the pattern kernels and what the gfx950 compile gives
+ * them: "... vgpr_f32=.. vgpr_f64=.. waves_f32=.. waves_f64=.." (the row
+ * kernels of a round without terms and without a row scale; DESIGN.md,
+ * "Pattern-only CSR", has every instantiation next to the values kernels';
+ * tools/bench_csr_pattern.py records it).  No GPU needed. */
+const char* st_csr_pattern_shape_desc(void);
+/* The host-pointer twin: validates ON THE HOST, before the queue is even
+ * looked at, with the device path's predicates and messages - dtype, opt's
+ * flags, `flags` (ST_CSR_EMPTY_ROWS_OK), n, row_ptr, the columns, the scales
+ * (row_scale before col_scale, the lowest index), K in [0,
+ * ST_CSR_TERMS_MAX], the term vectors, the rows of the operator, and without
+ * terms the empty rows - then copies in, solves, copies out.  row_scale /
+ * col_scale may be NULL; K = 0 takes NULL u / w.  Returns h2d + loop ms or
+ * negative. */
+int64_t max_eigen_value_csr_pattern_ex(void* wq, int dtype, uint32_t n, uint64_t nnz,
+                                       const int64_t* row_ptr, const int32_t* col_idx,
+                                       const void* row_scale, const void* col_scale,
+                                       uint32_t K, const void* const* u,
+                                       const void* const* w, unsigned int flags,
+                                       void* eigen_val, void* eigen_vec,
+                                       unsigned int* iter_cnt, const st_options* opt,
+                                       st_stats* stats);
+
+/* ---------------------------------------------------------------------- */
 /* 4. step-level kernels (asynchronous on `stream`, a hipStream_t or NULL) */
 /* ---------------------------------------------------------------------- */
 
@@ -1297,6 +1404,20 @@ int st_csr_terms_round(void* csr, void* terms, const void* d_s_prev,
 int st_csr_product_rowsum(void* csr_b, void* csr_a, void* d_s, void* d_scratch,
                           void* stream);
 int st_csr_product_round(void* csr_b, void* csr_a, const void* d_s_prev,
+                         void* d_s_next, const void* d_v_prev, void* d_v_cur,
+                         void* d_scratch, double eps, unsigned int k,
+                         unsigned int max_itr, unsigned int semantics,
+                         st_state* d_state, void* stream);
+/* The two steps on the pattern operator diag(r) P diag(c) (section 3h; what
+ * st_solve_csr_pattern runs): `pat` a st_csr_pattern_create handle, `terms` a
+ * st_csr_pattern_terms_create object of it or NULL, d_scratch
+ * st_csr_pattern_scratch_bytes(n, K) bytes (K = 0 without terms), 256-byte
+ * aligned.  After a round z = c * x stands behind the partials (x itself
+ * where c is NULL) and, with terms, dots[K] at the start.  The row sum works
+ * on an empty-rows handle; the round without terms refuses one. */
+int st_csr_pattern_rowsum(void* pat, void* terms, void* d_s, void* d_scratch,
+                          void* stream);
+int st_csr_pattern_round(void* pat, void* terms, const void* d_s_prev,
                          void* d_s_next, const void* d_v_prev, void* d_v_cur,
                          void* d_scratch, double eps, unsigned int k,
                          unsigned int max_itr, unsigned int semantics,
