@@ -16,9 +16,18 @@
 //     derives m_k/stop_k from its own sweep of s_k; workgroup 0 records)
 //     A_{k+1} = D_k^-1 A_k D_k in place, s_{k+1} = rowsum(A_{k+1})
 //     (launches after the stop round return at once)
+// What the loop works on is one Operator value: the dense matrix (transformed
+// in place as above, or only read with ST_FLAG_MATRIX_FREE), a 16-bit matrix,
+// a CSR handle, CSR plus terms, the product of two handles, or a pattern
+// handle with optional terms.  Every read-only kind runs the matrix-free
+// loop; op_rowsum and op_round are the only places that tell the kinds apart.
 // A batch of matrices runs k_solve_batched (one launch, a workgroup per
 // matrix) or, with ST_FLAG_BATCH_ROUNDS, this loop with every launch
-// covering the whole batch (k_round_batched, solve_batched_rounds).
+// covering the whole batch (k_round_batched, solve_batched_rounds).  The
+// batched forms that enqueue rounds (solve_batched_rounds, the batched and
+// the multi-column CSR solves) share counted_rounds; all five batched forms
+// share report_entries.  The host-pointer twins lay their workspace out with
+// CsrSlots / VecSlots and end in finish_twin.
 // The reference blocks on a host_accessor every round
 // (similarity_transform.cpp:45-50).  Here rounds are enqueued in batches;
 // the host checks the device `done` flag of batch b while batch b+1 is
@@ -64,38 +73,73 @@ namespace {
 constexpr uint32_t kDefaultBatch = 8;
 constexpr uint32_t kFlatBatch = 2;
 
+constexpr size_t
+up256(size_t b)
+{
+  return (b + 255) & ~(size_t)255;
+}
+
+// a device allocation that only grows: ensure() keeps what is large enough,
+// else waits for the stream's work on the old one, frees it and allocates
+struct DeviceBuf
+{
+  void* p = nullptr;
+  size_t cap = 0; // bytes
+  int ensure(hipStream_t stream, size_t bytes)
+  {
+    if (p && cap >= bytes)
+      return 0;
+    if (p) {
+      ST_CHECK(hipStreamSynchronize(stream));
+      ST_CHECK(hipFree(p));
+      p = nullptr;
+      cap = 0;
+    }
+    ST_CHECK(hipMalloc(&p, bytes));
+    cap = bytes;
+    return 0;
+  }
+  void release()
+  {
+    if (p)
+      (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// slots of Context::vec and of Context::bsum
+constexpr size_t kVecSlots = 4 + 2 * (kDeferRoundsMax + 1);
+constexpr size_t kBsumSlots = 3;
+
 struct Context
 {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr; // own_stream or a caller stream
   // cached device workspaces (grown on demand, freed by destroy_queue)
-  void* d_mat = nullptr;
-  size_t mat_bytes = 0;
+  DeviceBuf mat; // the host twins' copy of their matrix
   // [s0 | s1 | v | v' | s ring (kDeferRoundsMax + 1) | 1/s ring (same)],
   // each vec_bytes
-  void* d_vec = nullptr;
+  DeviceBuf vec;
   size_t vec_bytes = 0;
-  void* d_part = nullptr; // flat-round partial sums (large matrices)
-  size_t part_bytes = 0;
+  DeviceBuf part; // flat-round partial sums (large matrices)
   st_state* d_state = nullptr;
   st_state* h_state = nullptr; // pinned, 2 slots
   std::vector<float> round_ms; // per-round kernel time of the last timed solve
   // ST_FLAG_TRACE_SUMS: the row sums s_k every round of the last traced
   // solve evaluated (device staging, then the host copy st_last_round_sums
   // returns)
-  void* d_trace = nullptr;
-  size_t trace_cap = 0;
-  std::vector<unsigned char> trace;
+  DeviceBuf trace;
+  std::vector<unsigned char> trace_sums;
   uint32_t trace_rounds = 0;
   hipEvent_t ev_flag[2] = { nullptr, nullptr };
   // batched solve: one st_state per matrix (device array and its host copy)
-  st_state* d_bstate = nullptr;
-  size_t bstate_cap = 0; // states
+  DeviceBuf bstate;
   std::vector<st_state> h_bstate;
   // batched round loop: [s0 | s1 | v], each bsum_bytes ([batch][n]); the
   // count of finished matrices and its pinned host mirror (2 slots)
-  void* d_bsum = nullptr;
+  DeviceBuf bsum;
   size_t bsum_bytes = 0;
   uint32_t* d_bcount = nullptr;
   uint32_t* h_bcount = nullptr;
@@ -106,6 +150,18 @@ struct Context
   void* h_vb = nullptr;
   void* d_vb = nullptr;
   size_t vb_cap = 0; // matrices
+
+  template <typename T>
+  T* vec_slot(size_t i) const
+  {
+    return reinterpret_cast<T*>(static_cast<char*>(vec.p) + i * vec_bytes);
+  }
+  template <typename T>
+  T* bsum_slot(size_t i) const
+  {
+    return reinterpret_cast<T*>(static_cast<char*>(bsum.p) + i * bsum_bytes);
+  }
+  st_state* d_bstate() const { return static_cast<st_state*>(bstate.p); }
 };
 
 // bytes of the descriptor table for `count` matrices
@@ -133,86 +189,21 @@ ensure_device(Context* c)
 int
 ensure_vectors(Context* c, size_t vec_bytes)
 {
-  vec_bytes = (vec_bytes + 255) & ~(size_t)255;
-  if (c->d_vec && c->vec_bytes >= vec_bytes)
-    return 0;
-  if (c->d_vec) {
-    ST_CHECK(hipStreamSynchronize(c->stream));
-    ST_CHECK(hipFree(c->d_vec));
-    c->d_vec = nullptr;
-  }
-  ST_CHECK(hipMalloc(&c->d_vec, (4 + 2 * (kDeferRoundsMax + 1)) * vec_bytes));
-  c->vec_bytes = vec_bytes;
-  return 0;
-}
-
-int
-ensure_part(Context* c, size_t bytes)
-{
-  if (c->d_part && c->part_bytes >= bytes)
-    return 0;
-  if (c->d_part) {
-    ST_CHECK(hipStreamSynchronize(c->stream));
-    ST_CHECK(hipFree(c->d_part));
-    c->d_part = nullptr;
-    c->part_bytes = 0;
-  }
-  ST_CHECK(hipMalloc(&c->d_part, bytes));
-  c->part_bytes = bytes;
-  return 0;
-}
-
-int
-ensure_matrix(Context* c, size_t bytes)
-{
-  if (c->d_mat && c->mat_bytes >= bytes)
-    return 0;
-  if (c->d_mat) {
-    ST_CHECK(hipStreamSynchronize(c->stream));
-    ST_CHECK(hipFree(c->d_mat));
-    c->d_mat = nullptr;
-    c->mat_bytes = 0;
-  }
-  ST_CHECK(hipMalloc(&c->d_mat, bytes));
-  c->mat_bytes = bytes;
-  return 0;
-}
-
-// a traced solve records every evaluated round's n row sums: at most
-// kTraceMaxBytes of them (tests and diagnostics, not a production mode)
-constexpr size_t kTraceMaxBytes = (size_t)1 << 30;
-
-int
-ensure_trace(Context* c, size_t bytes)
-{
-  if (c->d_trace && c->trace_cap >= bytes)
-    return 0;
-  if (c->d_trace) {
-    ST_CHECK(hipStreamSynchronize(c->stream));
-    ST_CHECK(hipFree(c->d_trace));
-    c->d_trace = nullptr;
-    c->trace_cap = 0;
-  }
-  ST_CHECK(hipMalloc(&c->d_trace, bytes));
-  c->trace_cap = bytes;
+  if (c->vec.ensure(c->stream, kVecSlots * up256(vec_bytes)))
+    return -1;
+  c->vec_bytes = c->vec.cap / kVecSlots;
   return 0;
 }
 
 int
 ensure_bstate(Context* c, size_t count)
 {
-  if (c->d_bstate && c->bstate_cap >= count)
-    return 0;
-  if (c->d_bstate) {
-    ST_CHECK(hipStreamSynchronize(c->stream));
-    ST_CHECK(hipFree(c->d_bstate));
-    c->d_bstate = nullptr;
-    c->bstate_cap = 0;
-  }
-  ST_CHECK(hipMalloc((void**)&c->d_bstate, count * sizeof(st_state)));
-  c->bstate_cap = count;
-  return 0;
+  return c->bstate.ensure(c->stream, count * sizeof(st_state));
 }
+
+// a traced solve records every evaluated round's n row sums: at most
+// kTraceMaxBytes of them (tests and diagnostics, not a production mode)
+constexpr size_t kTraceMaxBytes = (size_t)1 << 30;
 
 int
 ensure_vbatch(Context* c, size_t count)
@@ -238,22 +229,14 @@ ensure_vbatch(Context* c, size_t count)
 int
 ensure_bsum(Context* c, size_t bytes)
 {
-  bytes = (bytes + 255) & ~(size_t)255;
   if (!c->d_bcount)
     ST_CHECK(hipMalloc((void**)&c->d_bcount, sizeof(uint32_t)));
   if (!c->h_bcount)
     ST_CHECK(hipHostMalloc((void**)&c->h_bcount, 2 * sizeof(uint32_t),
                            hipHostMallocCoherent | hipHostMallocMapped));
-  if (c->d_bsum && c->bsum_bytes >= bytes)
-    return 0;
-  if (c->d_bsum) {
-    ST_CHECK(hipStreamSynchronize(c->stream));
-    ST_CHECK(hipFree(c->d_bsum));
-    c->d_bsum = nullptr;
-    c->bsum_bytes = 0;
-  }
-  ST_CHECK(hipMalloc(&c->d_bsum, 3 * bytes));
-  c->bsum_bytes = bytes;
+  if (c->bsum.ensure(c->stream, kBsumSlots * up256(bytes)))
+    return -1;
+  c->bsum_bytes = c->bsum.cap / kBsumSlots;
   return 0;
 }
 
@@ -309,34 +292,145 @@ resolve(const st_options* opt, Resolved* r)
   return 0;
 }
 
-// The round loop on a device-resident matrix (transformed in place).
-// flush_matrix: leave the matrix as the every-round loop would (the caller
-// sees it); a private copy (solve_host) skips the deferred loop's last store.
-// storage != 0 (ST_STORE_F16 / ST_STORE_BF16, T = float): d_mat holds n x n
-// 16-bit elements and is read only - the matrix-free loop with the launchers
-// of st_half.hip for K0 and the round (solve_device_half checks the options)
-// csr != nullptr: the matrix is that CSR handle (d_mat is not dereferenced) -
-// the same matrix-free loop with st_csr.hip's K0 and two-launch round, x in
-// the first (here unused) slot of the deferred ring; with `terms` the
-// operator is A + sum_j u_j w_j^T (st_csr_terms.hip's K0 and three-launch
-// round, dots and partials in the flat scratch, unused here); with `csr_b`
-// the operator is the product csr_b * csr (st_csr_product.hip's K0 and
-// three-launch round, y in the second slot of the ring)
-// pat != nullptr (csr is null then): the pattern-only operator of that handle
-// (st_csr_pattern.hip's launch 0 and round, z where the CSR round keeps x,
-// `terms` a terms object of the pattern handle or null)
+// What a solve_device loop works on.  A dense matrix is transformed in place
+// (k_round, flat, deferred, single launch) or, with ST_FLAG_MATRIX_FREE, only
+// read; every other kind is read only and runs the matrix-free loop with its
+// own launch 0 (op_rowsum) and round (op_round).  The named constructors are
+// the only way to make one, so no other combination of handles exists.
+struct Operator
+{
+  enum Kind { kDense, kHalf, kCsr, kCsrTerms, kProduct, kPattern };
+  Kind kind;
+  uint32_t n;
+  void* mat;                   // kDense: n x n of the vectors' type; kHalf: 16-bit elements
+  int storage;                 // kHalf: ST_STORE_F16 / ST_STORE_BF16
+  const CsrHandle* a;          // kCsr, kCsrTerms; kProduct: the right factor
+  const CsrHandle* b;          // kProduct: the left factor of B A
+  const CsrTermsHandle* terms; // kCsrTerms; kPattern: its terms object or null
+  const CsrPatternHandle* pat; // kPattern
+
+  static Operator dense(void* d_mat, uint32_t n)
+  {
+    return { kDense, n, d_mat, 0, nullptr, nullptr, nullptr, nullptr };
+  }
+  // fp32 vectors only; the loop never writes through d_mat
+  static Operator half(int storage, const void* d_mat, uint32_t n)
+  {
+    return { kHalf, n, const_cast<void*>(d_mat), storage,
+             nullptr, nullptr, nullptr, nullptr };
+  }
+  static Operator csr(const CsrHandle* h)
+  {
+    return { kCsr, h->n, nullptr, 0, h, nullptr, nullptr, nullptr };
+  }
+  // A + sum_j u_j w_j^T
+  static Operator csr_terms(const CsrHandle* h, const CsrTermsHandle* t)
+  {
+    return { kCsrTerms, h->n, nullptr, 0, h, nullptr, t, nullptr };
+  }
+  // B A, never formed
+  static Operator product(const CsrHandle* b, const CsrHandle* a)
+  {
+    return { kProduct, a->n, nullptr, 0, a, b, nullptr, nullptr };
+  }
+  // diag(r) P diag(c) [+ sum_j u_j w_j^T]
+  static Operator pattern(const CsrPatternHandle* p, const CsrTermsHandle* t)
+  {
+    return { kPattern, p->n, nullptr, 0, nullptr, nullptr, t, p };
+  }
+  bool read_only() const { return kind != kDense; }
+};
+
+// the loop's buffers a read-only operator works in besides s and v: x (the
+// pattern's z) in the first slot of the deferred ring, the product's y in its
+// second, dots and partials (terms; the flat K0's partials) in the flat scratch
+template <typename T>
+struct OpScratch
+{
+  T* x;
+  T* y;
+  T* part;
+};
+
+// launch 0: s0 = the row sums of the operator (`flat`: the dense K0 in its
+// flat form, w.part sized for it)
+template <typename T>
+int
+op_rowsum(const Operator& op, T* s0, const OpScratch<T>& w, bool flat, hipStream_t s)
+{
+  switch (op.kind) {
+    case Operator::kPattern:
+      return launch_csr_pattern_rowsum(op.pat, op.terms, s0, w.part, s);
+    case Operator::kProduct:
+      return launch_csr_product_rowsum(op.b, op.a, s0, w.y, s);
+    case Operator::kCsrTerms:
+      return launch_csr_terms_rowsum(op.a, op.terms, s0, w.part, s);
+    case Operator::kCsr:
+      return launch_csr_rowsum(op.a, s0, s);
+    case Operator::kHalf:
+      if constexpr (std::is_same<T, float>::value)
+        return launch_rowsum_half(op.storage, op.mat, s0, op.n, op.n, s);
+      else
+        return 0;
+    case Operator::kDense: {
+      const T* a = static_cast<const T*>(op.mat);
+      return flat ? launch_rowsum_flat<T>(a, s0, w.part, op.n, op.n, s)
+                  : launch_rowsum<T>(a, s0, op.n, op.n, s);
+    }
+  }
+  return 0;
+}
+
+// the matrix-free round: launch number `launch` = k + 1 evaluates round k
+template <typename T>
+int
+op_round(const Operator& op, const T* s_prev, T* s_next, const T* v_prev, T* v_cur,
+         const OpScratch<T>& w, const Resolved& o, uint32_t launch, st_state* st,
+         hipStream_t s)
+{
+  switch (op.kind) {
+    case Operator::kPattern:
+      return launch_csr_pattern_round(op.pat, op.terms, s_prev, s_next, v_prev, v_cur, w.x,
+                                      w.part, o.eps, launch, o.max_itr, o.semantics, st, s);
+    case Operator::kProduct:
+      return launch_csr_product_round(op.b, op.a, s_prev, s_next, v_prev, v_cur, w.x, w.y,
+                                      o.eps, launch, o.max_itr, o.semantics, st, s);
+    case Operator::kCsrTerms:
+      return launch_csr_terms_round(op.a, op.terms, s_prev, s_next, v_prev, v_cur, w.x,
+                                    w.part, o.eps, launch, o.max_itr, o.semantics, st, s);
+    case Operator::kCsr:
+      return launch_csr_round(op.a, s_prev, s_next, v_prev, v_cur, w.x, o.eps, launch,
+                              o.max_itr, o.semantics, st, s);
+    case Operator::kHalf:
+      if constexpr (std::is_same<T, float>::value)
+        return launch_mfree_half(op.storage, op.mat, s_prev, s_next, v_prev, v_cur, op.n,
+                                 op.n, 0, (T)o.eps, launch, o.max_itr, o.semantics, st, s);
+      else
+        return 0;
+    case Operator::kDense:
+      return launch_mfree<T>(static_cast<const T*>(op.mat), s_prev, s_next, v_prev, v_cur,
+                             op.n, op.n, 0, (T)o.eps, launch, o.max_itr, o.semantics, st, s);
+  }
+  return 0;
+}
+
+// The round loop on a device-resident operator.
+// flush_matrix (a dense matrix transformed in place): leave the matrix as the
+// every-round loop would (the caller sees it); a private copy (solve_host)
+// skips the deferred loop's last store.
 template <typename T>
 int64_t
-solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
-             T* eigen_val, uint32_t* iter_cnt, const st_options* opt,
-             st_stats* stats, bool flush_matrix = true, int storage = 0,
-             const CsrHandle* csr = nullptr, const CsrTermsHandle* terms = nullptr,
-             const CsrHandle* csr_b = nullptr, const CsrPatternHandle* pat = nullptr)
+solve_device(Context* c, const Operator& op, T* d_v_out, T* v_host, T* eigen_val,
+             uint32_t* iter_cnt, const st_options* opt, st_stats* stats,
+             bool flush_matrix = true)
 {
   static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value,
                 "fp32 / fp64 vectors");
+  const uint32_t n = op.n;
+  T* const d_mat = static_cast<T*>(op.mat); // kDense only
   ST_REQUIRE(c, "null queue");
-  ST_REQUIRE(d_mat, "null matrix");
+  if (op.kind == Operator::kDense || op.kind == Operator::kHalf)
+    ST_REQUIRE(op.mat, "null matrix");
   ST_REQUIRE(n > 0, "dim must be > 0");
   ST_REQUIRE(eigen_val && iter_cnt, "null output pointer");
   ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
@@ -346,26 +440,24 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   if (ensure_device(c) || ensure_vectors(c, sizeof(T) * (size_t)n))
     return -1;
   hipStream_t s = c->stream;
-  T* s_buf[2] = { reinterpret_cast<T*>(c->d_vec),
-                  reinterpret_cast<T*>((char*)c->d_vec + c->vec_bytes) };
-  T* d_v = d_v_out ? d_v_out
-                   : reinterpret_cast<T*>((char*)c->d_vec + 2 * c->vec_bytes);
+  T* s_buf[2] = { c->vec_slot<T>(0), c->vec_slot<T>(1) };
+  T* d_v = d_v_out ? d_v_out : c->vec_slot<T>(2);
   // matrix-free ping-pong partner of d_v
-  T* d_v2 = reinterpret_cast<T*>((char*)c->d_vec + 3 * c->vec_bytes);
+  T* d_v2 = c->vec_slot<T>(3);
   T* vb[2] = { d_v, d_v2 };
   const bool timed = (o.flags & ST_FLAG_TIME_KERNELS) != 0;
   const bool traced = (o.flags & ST_FLAG_TRACE_SUMS) != 0;
   const size_t row_bytes = sizeof(T) * (size_t)n;
-  c->trace.clear();
+  c->trace_sums.clear();
   c->trace_rounds = 0;
   if (traced) {
     ST_REQUIRE(row_bytes * o.max_itr <= kTraceMaxBytes,
                "ST_FLAG_TRACE_SUMS: %u rounds x %u row sums exceed the %zu MiB "
                "trace; lower max_itr", o.max_itr, n, kTraceMaxBytes >> 20);
-    if (ensure_trace(c, row_bytes * o.max_itr))
+    if (c->trace.ensure(s, row_bytes * o.max_itr))
       return -1;
   }
-  const bool mfree = storage != 0 || csr || pat || (o.flags & ST_FLAG_MATRIX_FREE) != 0;
+  const bool mfree = op.read_only() || (o.flags & ST_FLAG_MATRIX_FREE) != 0;
   // large matrices: the flat round (k_flat + k_parts)
   const bool flat = !mfree && round_flat_pays(n, n, sizeof(T));
   // the flat round stores the matrix every kDefer rounds (bit-identical
@@ -376,20 +468,19 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   T* ring_s[kDeferRoundsMax + 1];
   T* ring_inv[kDeferRoundsMax + 1];
   for (uint32_t i = 0; i < kR; i++) {
-    ring_s[i] = reinterpret_cast<T*>((char*)c->d_vec + (4 + i) * c->vec_bytes);
-    ring_inv[i] = reinterpret_cast<T*>((char*)c->d_vec +
-                                       (4 + kDeferRoundsMax + 1 + i) * c->vec_bytes);
+    ring_s[i] = c->vec_slot<T>(4 + i);
+    ring_inv[i] = c->vec_slot<T>(4 + kDeferRoundsMax + 1 + i);
   }
   // K0 takes the flat form wherever the flat round pays (the matrix-free
   // loop's too)
-  const bool flat_k0 = storage == 0 && !csr && !pat && round_flat_pays(n, n, sizeof(T));
-  if (flat_k0 && ensure_part(c, sizeof(T) * round_flat_scratch(n, n)))
+  const bool flat_k0 = !op.read_only() && round_flat_pays(n, n, sizeof(T));
+  if (flat_k0 && c->part.ensure(s, sizeof(T) * round_flat_scratch(n, n)))
     return -1;
-  if (terms && ensure_part(c, csr_terms_dots_bytes(terms->K)))
+  if (op.terms && c->part.ensure(s, csr_terms_dots_bytes(op.terms->K)))
     return -1;
-  T* d_part = reinterpret_cast<T*>(c->d_part);
-  // the product round's y: the ring's second slot (x is its first)
-  T* const d_y = reinterpret_cast<T*>((char*)c->d_vec + 5 * c->vec_bytes);
+  T* d_part = reinterpret_cast<T*>(c->part.p);
+  // (the deferred ring is the dense loop's: free in every read-only one)
+  const OpScratch<T> scratch{ c->vec_slot<T>(4), c->vec_slot<T>(5), d_part };
   // rounds per host flag check: the launches queued behind the stopping
   // round still run as gated no-ops, and a gated flat round is two launches
   // of up to millions of workgroups (~10 us each), so the flat form checks
@@ -431,21 +522,7 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
     (void)hipEventRecord(ev[0], s);
   }
   T* const s0 = defer ? ring_s[0] : s_buf[0];
-  if (pat) { // launch 0 on the pattern operator
-    if (launch_csr_pattern_rowsum(pat, terms, s0, d_part, s))
-      return -1;
-  } else if (csr) { // K0 on the CSR matrix
-    if (csr_b    ? launch_csr_product_rowsum(csr_b, csr, s0, d_y, s)
-        : terms ? launch_csr_terms_rowsum(csr, terms, s0, d_part, s)
-                : launch_csr_rowsum(csr, s0, s))
-      return -1;
-  } else if (storage != 0) { // K0 on the 16-bit matrix
-    if constexpr (std::is_same<T, float>::value) {
-      if (launch_rowsum_half(storage, d_mat, s0, n, n, s))
-        return -1;
-    }
-  } else if (!single && (flat_k0 ? launch_rowsum_flat<T>(d_mat, s0, d_part, n, n, s)
-                                 : launch_rowsum<T>(d_mat, s0, n, n, s))) // K0
+  if (!single && op_rowsum<T>(op, s0, scratch, flat_k0, s)) // K0
     return -1;
   if (defer && launch_recip<T>(ring_s[0], ring_inv[0], n, s))
     return -1;
@@ -468,7 +545,7 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
       const uint32_t k = enqueued + j;
       hipEvent_t ea = nullptr, eb = nullptr;
       if (traced) // s_k, the row sums round k evaluates (no-op copies past the stop)
-        rc |= hipMemcpyAsync((char*)c->d_trace + (size_t)k * row_bytes,
+        rc |= hipMemcpyAsync((char*)c->trace.p + (size_t)k * row_bytes,
                              defer ? ring_s[k % kR] : s_buf[cur], row_bytes,
                              hipMemcpyDeviceToDevice, s) != hipSuccess;
       if (timed) {
@@ -477,34 +554,9 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
         ev.push_back(eb);
         (void)hipEventRecord(ea, s);
       }
-      if (pat) // launch k+1 evaluates round k
-        rc |= launch_csr_pattern_round(pat, terms, s_buf[cur], s_buf[cur ^ 1],
-                                       vb[k & 1], vb[(k + 1) & 1], ring_s[0], d_part,
-                                       o.eps, k + 1, o.max_itr, o.semantics,
-                                       c->d_state, s);
-      else if (csr && csr_b) // launch k+1 evaluates round k
-        rc |= launch_csr_product_round(csr_b, csr, s_buf[cur], s_buf[cur ^ 1],
-                                       vb[k & 1], vb[(k + 1) & 1], ring_s[0],
-                                       d_y, o.eps, k + 1, o.max_itr,
-                                       o.semantics, c->d_state, s);
-      else if (csr && terms)
-        rc |= launch_csr_terms_round(csr, terms, s_buf[cur], s_buf[cur ^ 1],
-                                     vb[k & 1], vb[(k + 1) & 1], ring_s[0], d_part,
-                                     o.eps, k + 1, o.max_itr, o.semantics,
-                                     c->d_state, s);
-      else if (csr)
-        rc |= launch_csr_round(csr, s_buf[cur], s_buf[cur ^ 1], vb[k & 1],
-                               vb[(k + 1) & 1], ring_s[0], o.eps, k + 1,
-                               o.max_itr, o.semantics, c->d_state, s);
-      else if (storage != 0) { // launch k+1 evaluates round k
-        if constexpr (std::is_same<T, float>::value)
-          rc |= launch_mfree_half(storage, d_mat, s_buf[cur], s_buf[cur ^ 1],
-                                  vb[k & 1], vb[(k + 1) & 1], n, n, 0, eps,
-                                  k + 1, o.max_itr, o.semantics, c->d_state, s);
-      } else if (mfree)
-        rc |= launch_mfree<T>(d_mat, s_buf[cur], s_buf[cur ^ 1], vb[k & 1],
-                              vb[(k + 1) & 1], n, n, 0, eps, k + 1, o.max_itr,
-                              o.semantics, c->d_state, s);
+      if (mfree) // launch k+1 evaluates round k
+        rc |= op_round<T>(op, s_buf[cur], s_buf[cur ^ 1], vb[k & 1], vb[(k + 1) & 1],
+                          scratch, o, k + 1, c->d_state, s);
       else if (defer) {
         // stored: A_j, j = the last multiple of kDefer <= k
         const uint32_t j0 = k - k % kDefer, np = k - j0;
@@ -579,8 +631,8 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
                        hipMemcpyDeviceToHost));
   const double d2h_ms = ms_since(t1);
   if (traced) { // rounds 0 .. end-1 were evaluated
-    c->trace.resize(row_bytes * fin.end);
-    ST_CHECK(hipMemcpy(c->trace.data(), c->d_trace, c->trace.size(),
+    c->trace_sums.resize(row_bytes * fin.end);
+    ST_CHECK(hipMemcpy(c->trace_sums.data(), c->trace.p, c->trace_sums.size(),
                        hipMemcpyDeviceToHost));
     c->trace_rounds = fin.end;
   }
@@ -614,6 +666,37 @@ solve_device(Context* c, T* d_mat, uint32_t n, T* d_v_out, T* v_host,
   return (int64_t)loop_ms;
 }
 
+// solve_device on a handle's operator, in the handle's dtype
+int64_t
+solve_operator(Context* c, const Operator& op, int dtype, void* d_v_out, void* v_host,
+               void* eigen_val, uint32_t* iter_cnt, const st_options* opt, st_stats* stats)
+{
+  if (dtype)
+    return solve_device<double>(c, op, static_cast<double*>(d_v_out),
+                                static_cast<double*>(v_host),
+                                static_cast<double*>(eigen_val), iter_cnt, opt, stats);
+  return solve_device<float>(c, op, static_cast<float*>(d_v_out),
+                             static_cast<float*>(v_host), static_cast<float*>(eigen_val),
+                             iter_cnt, opt, stats);
+}
+
+// What every host-pointer twin ends with: the copy-in's milliseconds (and the
+// device transposition's, tr_ms >= 0, in microseconds clamped to the field)
+// into the solve's stats, those to the caller; returns the call's milliseconds
+int64_t
+finish_twin(st_stats local, double h2d, st_stats* stats, double tr_ms = -1.0)
+{
+  local.h2d_ms = h2d;
+  if (tr_ms >= 0.0) {
+    const double us = tr_ms * 1000.0;
+    local.transpose_us = us < 4294967295.0 ? (uint32_t)us : 0xffffffffu;
+    h2d += tr_ms;
+  }
+  if (stats)
+    *stats = local;
+  return (int64_t)(h2d + local.loop_ms);
+}
+
 // The solve on a device-resident matrix stored in 16 bits (read only):
 // solve_device<float>'s matrix-free loop - gated batches, pinned state
 // mirror, v ping-pong, timing and tracing - with the 16-bit launchers.
@@ -633,10 +716,8 @@ solve_device_half(Context* c, int storage, const void* d_mat, uint32_t n,
              "ST_FLAG_BATCH_ROUNDS are not supported (flags = %u): the matrix "
              "is read only and every round is one launch", flags);
   ST_REQUIRE(((uintptr_t)d_mat & 1u) == 0, "half solve: matrix not 2-byte aligned");
-  // the loop never writes through this pointer when storage != 0
-  float* m = static_cast<float*>(const_cast<void*>(d_mat));
-  return solve_device<float>(c, m, n, d_v_out, v_host, eigen_val, iter_cnt, opt,
-                             stats, false, storage);
+  return solve_device<float>(c, Operator::half(storage, d_mat, n), d_v_out, v_host,
+                             eigen_val, iter_cnt, opt, stats);
 }
 
 int64_t
@@ -663,21 +744,18 @@ solve_host_half(Context* c, int storage, const void* mat, uint32_t n,
   if (ensure_device(c))
     return -1;
   const size_t bytes = 2 * (size_t)n * n;
-  if (ensure_matrix(c, bytes))
+  if (c->mat.ensure(c->stream, bytes))
     return -1;
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(c->d_mat, mat, bytes, hipMemcpyHostToDevice,
+  ST_CHECK(hipMemcpyAsync(c->mat.p, mat, bytes, hipMemcpyHostToDevice,
                           c->stream));
   ST_CHECK(hipStreamSynchronize(c->stream));
   const double h2d = ms_since(t0);
   st_stats local{};
-  if (solve_device_half(c, storage, c->d_mat, n, nullptr, eigen_vec, eigen_val,
+  if (solve_device_half(c, storage, c->mat.p, n, nullptr, eigen_vec, eigen_val,
                         iter_cnt, opt, &local) < 0)
     return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return finish_twin(local, h2d, stats);
 }
 
 // The solve on a validated CSR matrix (st_csr_create): solve_device's
@@ -696,19 +774,8 @@ solve_csr(Context* c, const CsrHandle* h, void* d_v_out, void* v_host,
   ST_REQUIRE(c->device == h->device,
              "csr solve: the matrix lives on device %d, the queue on %d",
              h->device, c->device);
-  // never dereferenced: solve_device reads the matrix through the handle
-  void* tag = const_cast<CsrHandle*>(h);
-  if (h->dtype)
-    return solve_device<double>(c, static_cast<double*>(tag), h->n,
-                                static_cast<double*>(d_v_out),
-                                static_cast<double*>(v_host),
-                                static_cast<double*>(eigen_val), iter_cnt, opt,
-                                stats, false, 0, h, terms);
-  return solve_device<float>(c, static_cast<float*>(tag), h->n,
-                             static_cast<float*>(d_v_out),
-                             static_cast<float*>(v_host),
-                             static_cast<float*>(eigen_val), iter_cnt, opt,
-                             stats, false, 0, h, terms);
+  return solve_operator(c, terms ? Operator::csr_terms(h, terms) : Operator::csr(h),
+                        h->dtype, d_v_out, v_host, eigen_val, iter_cnt, opt, stats);
 }
 
 // The solve on a validated pattern handle (st_csr_pattern_create): solve_csr
@@ -727,20 +794,93 @@ solve_csr_pattern(Context* c, const CsrPatternHandle* h, void* d_v_out, void* v_
   ST_REQUIRE(c->device == h->device,
              "csr pattern solve: the pattern lives on device %d, the queue on %d",
              h->device, c->device);
-  // never dereferenced: solve_device reads the pattern through the handle
-  void* tag = const_cast<CsrPatternHandle*>(h);
-  if (h->dtype)
-    return solve_device<double>(c, static_cast<double*>(tag), h->n,
-                                static_cast<double*>(d_v_out),
-                                static_cast<double*>(v_host),
-                                static_cast<double*>(eigen_val), iter_cnt, opt,
-                                stats, false, 0, nullptr, terms, nullptr, h);
-  return solve_device<float>(c, static_cast<float*>(tag), h->n,
-                             static_cast<float*>(d_v_out),
-                             static_cast<float*>(v_host),
-                             static_cast<float*>(eigen_val), iter_cnt, opt,
-                             stats, false, 0, nullptr, terms, nullptr, h);
+  return solve_operator(c, Operator::pattern(h, terms), h->dtype, d_v_out, v_host,
+                        eigen_val, iter_cnt, opt, stats);
 }
+
+// one host triple in the workspace at `base`: [row_ptr | vals | col_idx], each
+// at a 256-byte aligned offset (a pattern has no vals: b_val = 0)
+struct CsrSlots
+{
+  size_t b_ptr, b_val, b_col;
+  size_t bytes() const { return b_ptr + b_val + b_col; }
+  int64_t* ptr(char* base) const { return reinterpret_cast<int64_t*>(base); }
+  void* val(char* base) const { return base + b_ptr; }
+  int32_t* col(char* base) const { return reinterpret_cast<int32_t*>(base + b_ptr + b_val); }
+};
+
+CsrSlots
+csr_slots(int dtype, uint32_t n, uint64_t nnz, bool with_vals = true)
+{
+  const size_t elem = dtype ? 8 : 4;
+  return CsrSlots{ up256(8 * ((size_t)n + 1)), with_vals ? up256(elem * nnz) : 0,
+                   up256(4 * nnz) };
+}
+
+int
+csr_copy_in(Context* c, const CsrSlots& sl, char* base, int dtype, uint32_t n,
+            uint64_t nnz, const int64_t* row_ptr, const int32_t* col_idx,
+            const void* vals)
+{
+  const size_t elem = dtype ? 8 : 4;
+  ST_CHECK(hipMemcpyAsync(sl.ptr(base), row_ptr, 8 * ((size_t)n + 1),
+                          hipMemcpyHostToDevice, c->stream));
+  if (sl.b_val)
+    ST_CHECK(hipMemcpyAsync(sl.val(base), vals, elem * nnz, hipMemcpyHostToDevice,
+                            c->stream));
+  ST_CHECK(hipMemcpyAsync(sl.col(base), col_idx, 4 * nnz, hipMemcpyHostToDevice,
+                          c->stream));
+  return 0;
+}
+
+// one host triple into its slots at `base` and, once every copy queued so far
+// has landed, the validated handle over it (flags: csr_create's)
+int
+csr_stage(Context* c, const CsrSlots& sl, char* base, int dtype, uint32_t n,
+          uint64_t nnz, const int64_t* row_ptr, const int32_t* col_idx,
+          const void* vals, uint32_t flags, CsrHandle** out)
+{
+  if (csr_copy_in(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals))
+    return -1;
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  return csr_create(dtype, n, nnz, sl.ptr(base), sl.col(base), sl.val(base), c->stream,
+                    out, flags);
+}
+
+// n-vectors behind one another at `base`: vector i at the 256-byte aligned
+// slot base + i * stride
+struct VecSlots
+{
+  char* base;
+  size_t stride, bytes; // up256(bytes); one vector's elem * n
+  static size_t stride_of(int dtype, uint32_t n) { return up256((dtype ? 8 : 4) * (size_t)n); }
+  VecSlots(char* at, int dtype, uint32_t n)
+    : base(at), stride(stride_of(dtype, n)), bytes((dtype ? 8 : 4) * (size_t)n)
+  {
+  }
+  // the host vector `src` into slot i, *d_out <- its device address (a null
+  // src: no copy, a null address)
+  int copy_in(Context* c, size_t i, const void* src, const void** d_out) const
+  {
+    *d_out = nullptr;
+    if (!src)
+      return 0;
+    ST_CHECK(hipMemcpyAsync(base + i * stride, src, bytes, hipMemcpyHostToDevice,
+                            c->stream));
+    *d_out = base + i * stride;
+    return 0;
+  }
+  // K term pairs into slots first, first + 1, ...: [u_0 | w_0 | u_1 | ...]
+  int terms_in(Context* c, size_t first, uint32_t K, const void* const* u,
+               const void* const* w, const void** d_u, const void** d_w) const
+  {
+    for (uint32_t j = 0; j < K; j++)
+      if (copy_in(c, first + 2 * j, u[j], &d_u[j]) ||
+          copy_in(c, first + 2 * j + 1, w[j], &d_w[j]))
+        return -1;
+    return 0;
+  }
+};
 
 // The host-pointer solve of diag(r) P diag(c) + sum_j u_j w_j^T: everything
 // validated on the host first (dtype, opt's flags, flags, n, row_ptr, the
@@ -834,42 +974,25 @@ solve_host_csr_pattern(Context* c, int dtype, uint32_t n, uint64_t nnz,
   ST_REQUIRE(c, "null queue");
   if (ensure_device(c))
     return -1;
-  const size_t elem = dtype ? 8 : 4;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_col = up(4 * nnz),
-               b_vec = up(elem * (size_t)n);
-  if (ensure_matrix(c, b_ptr + b_col + (2 + 2 * (size_t)K) * b_vec))
+  const CsrSlots sl = csr_slots(dtype, n, nnz, false);
+  if (c->mat.ensure(c->stream,
+                    sl.bytes() + (2 + 2 * (size_t)K) * VecSlots::stride_of(dtype, n)))
     return -1;
-  char* base = static_cast<char*>(c->d_mat);
-  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
-  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr);
-  char* vec0 = base + b_ptr + b_col;
-  void* d_rs = row_scale ? vec0 : nullptr;
-  void* d_cs = col_scale ? vec0 + b_vec : nullptr;
+  char* base = static_cast<char*>(c->mat.p);
+  const VecSlots vs(base + sl.bytes(), dtype, n);
+  const void* d_rs = nullptr;
+  const void* d_cs = nullptr;
   const void* d_u[csr::kTermsMax] = {};
   const void* d_w[csr::kTermsMax] = {};
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1), hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice, c->stream));
-  if (d_rs)
-    ST_CHECK(hipMemcpyAsync(d_rs, row_scale, elem * (size_t)n, hipMemcpyHostToDevice,
-                            c->stream));
-  if (d_cs)
-    ST_CHECK(hipMemcpyAsync(d_cs, col_scale, elem * (size_t)n, hipMemcpyHostToDevice,
-                            c->stream));
-  for (uint32_t j = 0; j < K; j++) {
-    char* at = vec0 + (2 + 2 * (size_t)j) * b_vec;
-    ST_CHECK(hipMemcpyAsync(at, u[j], elem * (size_t)n, hipMemcpyHostToDevice,
-                            c->stream));
-    ST_CHECK(hipMemcpyAsync(at + b_vec, w[j], elem * (size_t)n, hipMemcpyHostToDevice,
-                            c->stream));
-    d_u[j] = at;
-    d_w[j] = at + b_vec;
-  }
+  if (csr_copy_in(c, sl, base, dtype, n, nnz, row_ptr, col_idx, nullptr) ||
+      vs.copy_in(c, 0, row_scale, &d_rs) || vs.copy_in(c, 1, col_scale, &d_cs) ||
+      vs.terms_in(c, 2, K, u, w, d_u, d_w))
+    return -1;
   ST_CHECK(hipStreamSynchronize(c->stream));
   CsrPatternHandle* h = nullptr;
-  if (csr_pattern_create(dtype, n, nnz, d_ptr, d_col, d_rs, d_cs, c->stream, &h, flags))
+  if (csr_pattern_create(dtype, n, nnz, sl.ptr(base), sl.col(base), d_rs, d_cs, c->stream,
+                         &h, flags))
     return -1;
   CsrTermsHandle* t = nullptr;
   if (K && csr_pattern_terms_create(h, K, d_u, d_w, c->stream, &t)) {
@@ -882,12 +1005,7 @@ solve_host_csr_pattern(Context* c, int dtype, uint32_t n, uint64_t nnz,
     solve_csr_pattern(c, h, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local, t);
   (void)csr_terms_destroy(t);
   (void)csr_pattern_destroy(h);
-  if (rc < 0)
-    return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return rc < 0 ? -1 : finish_twin(local, h2d, stats);
 }
 
 // The host-pointer solve of A + sum_j u_j w_j^T: everything validated on the
@@ -946,37 +1064,17 @@ solve_host_csr_terms(Context* c, int dtype, uint32_t n, uint64_t nnz,
   ST_REQUIRE(c, "null queue");
   if (ensure_device(c))
     return -1;
-  const size_t elem = dtype ? 8 : 4;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
-               b_col = up(4 * nnz), b_vec = up(elem * (size_t)n);
-  if (ensure_matrix(c, b_ptr + b_val + b_col + 2 * K * b_vec))
+  const CsrSlots sl = csr_slots(dtype, n, nnz);
+  if (c->mat.ensure(c->stream, sl.bytes() + 2 * K * VecSlots::stride_of(dtype, n)))
     return -1;
-  char* base = static_cast<char*>(c->d_mat);
-  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
-  void* d_val = base + b_ptr;
-  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  char* base = static_cast<char*>(c->mat.p);
+  const VecSlots vs(base + sl.bytes(), dtype, n);
   const void* d_u[csr::kTermsMax] = {};
   const void* d_w[csr::kTermsMax] = {};
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
-                          hipMemcpyHostToDevice, c->stream));
-  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  for (uint32_t j = 0; j < K; j++) {
-    char* at = base + b_ptr + b_val + b_col + 2 * j * b_vec;
-    ST_CHECK(hipMemcpyAsync(at, u[j], elem * (size_t)n, hipMemcpyHostToDevice,
-                            c->stream));
-    ST_CHECK(hipMemcpyAsync(at + b_vec, w[j], elem * (size_t)n,
-                            hipMemcpyHostToDevice, c->stream));
-    d_u[j] = at;
-    d_w[j] = at + b_vec;
-  }
-  ST_CHECK(hipStreamSynchronize(c->stream));
-  CsrHandle* h = nullptr;
-  if (csr_create(dtype, n, nnz, d_ptr, d_col, d_val, c->stream, &h, flags))
+  CsrHandle* h = nullptr; // (the vectors first: csr_stage waits for every copy)
+  if (vs.terms_in(c, 0, K, u, w, d_u, d_w) ||
+      csr_stage(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals, flags, &h))
     return -1;
   CsrTermsHandle* t = nullptr;
   if (csr_terms_create(h, K, d_u, d_w, c->stream, &t)) {
@@ -989,12 +1087,7 @@ solve_host_csr_terms(Context* c, int dtype, uint32_t n, uint64_t nnz,
     solve_csr(c, h, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local, t);
   (void)csr_terms_destroy(t);
   (void)csr_destroy(h);
-  if (rc < 0)
-    return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return rc < 0 ? -1 : finish_twin(local, h2d, stats);
 }
 
 // the context's cached device workspace holds the three arrays of a host
@@ -1016,38 +1109,20 @@ solve_host_csr(Context* c, int dtype, uint32_t n, uint64_t nnz,
   ST_REQUIRE(c, "null queue");
   if (ensure_device(c))
     return -1;
-  const size_t elem = dtype ? 8 : 4;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
-               b_col = up(4 * nnz);
-  if (ensure_matrix(c, b_ptr + b_val + b_col))
+  const CsrSlots sl = csr_slots(dtype, n, nnz);
+  if (c->mat.ensure(c->stream, sl.bytes()))
     return -1;
-  char* base = static_cast<char*>(c->d_mat);
-  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
-  void* d_val = base + b_ptr;
-  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  char* base = static_cast<char*>(c->mat.p);
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
-                          hipMemcpyHostToDevice, c->stream));
-  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipStreamSynchronize(c->stream));
   CsrHandle* h = nullptr;
-  if (csr_create(dtype, n, nnz, d_ptr, d_col, d_val, c->stream, &h))
+  if (csr_stage(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals, 0, &h))
     return -1;
   const double h2d = ms_since(t0);
   st_stats local{};
   const int64_t rc =
     solve_csr(c, h, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local);
   (void)csr_destroy(h);
-  if (rc < 0)
-    return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return rc < 0 ? -1 : finish_twin(local, h2d, stats);
 }
 
 // The LEFT Perron vector of a host matrix: solve_host_csr on T(A), which is
@@ -1072,34 +1147,20 @@ solve_host_csr_left(Context* c, int dtype, uint32_t n, uint64_t nnz,
   ST_REQUIRE(c, "null queue");
   if (ensure_device(c))
     return -1;
-  const size_t elem = dtype ? 8 : 4;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
-               b_col = up(4 * nnz), b_mat = b_ptr + b_val + b_col;
-  if (ensure_matrix(c, 2 * b_mat))
+  const CsrSlots sl = csr_slots(dtype, n, nnz);
+  if (c->mat.ensure(c->stream, 2 * sl.bytes()))
     return -1;
-  char* base = static_cast<char*>(c->d_mat);
-  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
-  void* d_val = base + b_ptr;
-  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
-  int64_t* d_tptr = reinterpret_cast<int64_t*>(base + b_mat);
-  void* d_tval = base + b_mat + b_ptr;
-  int32_t* d_tcol = reinterpret_cast<int32_t*>(base + b_mat + b_ptr + b_val);
+  char* base = static_cast<char*>(c->mat.p);
+  char* base_t = base + sl.bytes();
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
-                          hipMemcpyHostToDevice, c->stream));
-  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipStreamSynchronize(c->stream));
   CsrHandle* h = nullptr;
-  if (csr_create(dtype, n, nnz, d_ptr, d_col, d_val, c->stream, &h))
+  if (csr_stage(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals, 0, &h))
     return -1;
   const double h2d = ms_since(t0);
   const auto t1 = std::chrono::steady_clock::now();
   CsrHandle* ht = nullptr;
-  const int trc = csr_transpose(h, d_tptr, d_tcol, d_tval, c->stream, &ht);
+  const int trc =
+    csr_transpose(h, sl.ptr(base_t), sl.col(base_t), sl.val(base_t), c->stream, &ht);
   (void)csr_destroy(h);
   if (trc)
     return -1;
@@ -1108,14 +1169,7 @@ solve_host_csr_left(Context* c, int dtype, uint32_t n, uint64_t nnz,
   const int64_t rc =
     solve_csr(c, ht, nullptr, eigen_vec, eigen_val, iter_cnt, opt, &local);
   (void)csr_destroy(ht);
-  if (rc < 0)
-    return -1;
-  local.h2d_ms = h2d;
-  const double us = tr_ms * 1000.0;
-  local.transpose_us = us < 4294967295.0 ? (uint32_t)us : 0xffffffffu;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + tr_ms + local.loop_ms);
+  return rc < 0 ? -1 : finish_twin(local, h2d, stats, tr_ms);
 }
 
 // The solve on the product operator B A of two validated handles (never
@@ -1140,14 +1194,15 @@ solve_csr_product(Context* c, const CsrHandle* b, const CsrHandle* a, void* d_v_
   ST_REQUIRE(eigen_val && iter_cnt, "null output pointer");
   ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
   const size_t elem = a->dtype ? 8 : 4;
-  if (ensure_device(c) || ensure_vectors(c, elem * (size_t)a->n) || ensure_part(c, 256))
+  if (ensure_device(c) || ensure_vectors(c, elem * (size_t)a->n) ||
+      c->part.ensure(c->stream, 256))
     return -1;
   {
     // s_0 into the loop's own first buffer, y in the ring's second slot; the
     // solve computes both again
-    void* s0 = c->d_vec;
-    void* y = (char*)c->d_vec + 5 * c->vec_bytes;
-    unsigned long long* d_err = static_cast<unsigned long long*>(c->d_part);
+    void* s0 = c->vec_slot<char>(0);
+    void* y = c->vec_slot<char>(5);
+    unsigned long long* d_err = static_cast<unsigned long long*>(c->part.p);
     unsigned long long err = 0;
     ST_CHECK(hipMemsetAsync(d_err, 0xff, sizeof(err), c->stream));
     if (launch_csr_product_rowsum(b, a, s0, y, c->stream) ||
@@ -1162,52 +1217,8 @@ solve_csr_product(Context* c, const CsrHandle* b, const CsrHandle* a, void* d_v_
       return -1;
     }
   }
-  // never dereferenced: solve_device reads the matrices through the handles
-  void* tag = const_cast<CsrHandle*>(a);
-  if (a->dtype)
-    return solve_device<double>(c, static_cast<double*>(tag), a->n,
-                                static_cast<double*>(d_v_out),
-                                static_cast<double*>(v_host),
-                                static_cast<double*>(eigen_val), iter_cnt, opt,
-                                stats, false, 0, a, nullptr, b);
-  return solve_device<float>(c, static_cast<float*>(tag), a->n,
-                             static_cast<float*>(d_v_out), static_cast<float*>(v_host),
-                             static_cast<float*>(eigen_val), iter_cnt, opt, stats,
-                             false, 0, a, nullptr, b);
-}
-
-// one host triple into the workspace at `base`: [row_ptr | vals | col_idx],
-// each at a 256-byte aligned offset
-struct CsrSlots
-{
-  size_t b_ptr, b_val, b_col;
-  size_t bytes() const { return b_ptr + b_val + b_col; }
-  int64_t* ptr(char* base) const { return reinterpret_cast<int64_t*>(base); }
-  void* val(char* base) const { return base + b_ptr; }
-  int32_t* col(char* base) const { return reinterpret_cast<int32_t*>(base + b_ptr + b_val); }
-};
-
-CsrSlots
-csr_slots(int dtype, uint32_t n, uint64_t nnz)
-{
-  const size_t elem = dtype ? 8 : 4;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  return CsrSlots{ up(8 * ((size_t)n + 1)), up(elem * nnz), up(4 * nnz) };
-}
-
-int
-csr_copy_in(Context* c, const CsrSlots& sl, char* base, int dtype, uint32_t n,
-            uint64_t nnz, const int64_t* row_ptr, const int32_t* col_idx,
-            const void* vals)
-{
-  const size_t elem = dtype ? 8 : 4;
-  ST_CHECK(hipMemcpyAsync(sl.ptr(base), row_ptr, 8 * ((size_t)n + 1),
-                          hipMemcpyHostToDevice, c->stream));
-  ST_CHECK(hipMemcpyAsync(sl.val(base), vals, elem * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipMemcpyAsync(sl.col(base), col_idx, 4 * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  return 0;
+  return solve_operator(c, Operator::product(b, a), a->dtype, d_v_out, v_host, eigen_val,
+                        iter_cnt, opt, stats);
 }
 
 // The host-pointer solve of B A: everything validated on the host first
@@ -1242,9 +1253,9 @@ solve_host_csr_product(Context* c, int dtype, uint32_t n, uint64_t b_nnz,
   if (ensure_device(c))
     return -1;
   const CsrSlots sb = csr_slots(dtype, n, b_nnz), sa = csr_slots(dtype, n, a_nnz);
-  if (ensure_matrix(c, sb.bytes() + sa.bytes()))
+  if (c->mat.ensure(c->stream, sb.bytes() + sa.bytes()))
     return -1;
-  char* base_b = static_cast<char*>(c->d_mat);
+  char* base_b = static_cast<char*>(c->mat.p);
   char* base_a = base_b + sb.bytes();
   const auto t0 = std::chrono::steady_clock::now();
   if (csr_copy_in(c, sb, base_b, dtype, n, b_nnz, b_row_ptr, b_col_idx, b_vals) ||
@@ -1267,12 +1278,7 @@ solve_host_csr_product(Context* c, int dtype, uint32_t n, uint64_t b_nnz,
                                        iter_cnt, opt, &local);
   (void)csr_destroy(ha);
   (void)csr_destroy(hb);
-  if (rc < 0)
-    return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return rc < 0 ? -1 : finish_twin(local, h2d, stats);
 }
 
 // The Gram operators of ONE host matrix: side 0 = A^T A, 1 = A A^T.  Validated
@@ -1325,17 +1331,13 @@ solve_host_csr_gram(Context* c, int dtype, uint32_t n, uint64_t nnz,
   if (ensure_device(c))
     return -1;
   const CsrSlots sl = csr_slots(dtype, n, nnz);
-  if (ensure_matrix(c, 2 * sl.bytes()))
+  if (c->mat.ensure(c->stream, 2 * sl.bytes()))
     return -1;
-  char* base = static_cast<char*>(c->d_mat);
+  char* base = static_cast<char*>(c->mat.p);
   char* base_t = base + sl.bytes();
   const auto t0 = std::chrono::steady_clock::now();
-  if (csr_copy_in(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals))
-    return -1;
-  ST_CHECK(hipStreamSynchronize(c->stream));
   CsrHandle* h = nullptr;
-  if (csr_create(dtype, n, nnz, sl.ptr(base), sl.col(base), sl.val(base), c->stream, &h,
-                 csr::kEmptyRowsOk))
+  if (csr_stage(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals, csr::kEmptyRowsOk, &h))
     return -1;
   const double h2d = ms_since(t0);
   const auto t1 = std::chrono::steady_clock::now();
@@ -1354,14 +1356,95 @@ solve_host_csr_gram(Context* c, int dtype, uint32_t n, uint64_t nnz,
                                   &local);
   (void)csr_destroy(ht);
   (void)csr_destroy(h);
-  if (rc < 0)
-    return -1;
-  local.h2d_ms = h2d;
-  const double us = tr_ms * 1000.0;
-  local.transpose_us = us < 4294967295.0 ? (uint32_t)us : 0xffffffffu;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + tr_ms + local.loop_ms);
+  return rc < 0 ? -1 : finish_twin(local, h2d, stats, tr_ms);
+}
+
+// The counted round loop of the batched forms: round(k), k = 0, 1, ..., is
+// enqueued `per_check` at a time (the last batch cut at max_itr), then the
+// device's count of finished entries is mirrored into one of two pinned words
+// and an event recorded.  While that batch runs the host waits for the batch
+// before it and stops enqueuing once its count has reached `target`.  Returns
+// the rounds enqueued, -1 on an error.  round is a lambda: this loop is the
+// latency of a small batched call.
+template <typename Round>
+int64_t
+counted_rounds(Context* c, uint32_t per_check, uint32_t max_itr, uint32_t target,
+               Round&& round)
+{
+  hipStream_t s = c->stream;
+  uint32_t enqueued = 0, batch_no = 0;
+  bool done = false;
+  while (!done && enqueued < max_itr) {
+    const uint32_t b = (max_itr - enqueued) < per_check ? (max_itr - enqueued)
+                                                        : per_check;
+    for (uint32_t j = 0; j < b; j++)
+      if (round(enqueued + j))
+        return -1;
+    enqueued += b;
+    const int slot = batch_no & 1;
+    if (launch_count_mirror(c->d_bcount, &c->h_bcount[slot], s))
+      return -1;
+    ST_CHECK(hipEventRecord(c->ev_flag[slot], s));
+    // wait for the previous batch's count while this batch runs
+    if (batch_no > 0) {
+      ST_CHECK(hipEventSynchronize(c->ev_flag[slot ^ 1]));
+      done = c->h_bcount[slot ^ 1] >= target;
+    }
+    batch_no++;
+  }
+  return enqueued;
+}
+
+// What every batched form ends with, its states read back into res [count]
+// (Rec: st_state or CsrBatchResult) after loop_ms: per entry the done flag
+// (`noun` names the entry in the message), lambda, count and converged flag;
+// the eigenvectors to the host; the call's stats, `launches` in
+// fused_launches.  Returns the call's milliseconds.
+template <typename T, typename Rec>
+int64_t
+report_entries(const Rec* res, uint32_t count, const char* noun, T* eigen_vals,
+               uint32_t* iter_cnts, uint32_t* converged, T* v_host, const T* d_v,
+               size_t v_bytes, double loop_ms, uint32_t launches, st_stats* stats)
+{
+  const auto t1 = std::chrono::steady_clock::now();
+  uint32_t rounds = 0, all = 1;
+  for (uint32_t b = 0; b < count; b++) {
+    const Rec& fin = res[b];
+    ST_REQUIRE(fin.done, "internal: %s %u ended without done flag", noun, b);
+    eigen_vals[b] = (T)fin.lambda;
+    iter_cnts[b] = fin.iters;
+    if (converged)
+      converged[b] = fin.stop;
+    rounds = fin.end > rounds ? fin.end : rounds;
+    all &= fin.stop;
+  }
+  if (v_host)
+    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
+  const double d2h_ms = ms_since(t1);
+  if (stats) {
+    stats->loop_ms = loop_ms;
+    stats->d2h_ms = d2h_ms;
+    stats->rounds = rounds;
+    stats->converged = all;
+    stats->fused_launches = launches;
+  }
+  return (int64_t)loop_ms;
+}
+
+// the dense batched forms: the state array into the context's host copy first
+template <typename T>
+int64_t
+report_bstates(Context* c, uint32_t batch, T* eigen_vals, uint32_t* iter_cnts,
+               uint32_t* converged, T* v_host, const T* d_v, size_t v_bytes,
+               std::chrono::steady_clock::time_point t0, uint32_t launches,
+               st_stats* stats)
+{
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  c->h_bstate.resize(batch);
+  ST_CHECK(hipMemcpy(c->h_bstate.data(), c->bstate.p, sizeof(st_state) * (size_t)batch,
+                     hipMemcpyDeviceToHost));
+  return report_entries<T>(c->h_bstate.data(), batch, "matrix", eigen_vals, iter_cnts,
+                           converged, v_host, d_v, v_bytes, ms_since(t0), launches, stats);
 }
 
 // The solve of a validated batch in stacked CSR storage
@@ -1381,82 +1464,42 @@ solve_csr_batched_t(Context* c, const CsrBatchHandle* h, T* d_v_out, T* v_host,
   const uint32_t batch = h->batch;
   const size_t v_bytes = sizeof(T) * (size_t)h->n;
   if (ensure_device(c) || ensure_vectors(c, v_bytes) || ensure_bstate(c, batch) ||
-      ensure_bsum(c, 256) || ensure_part(c, sizeof(CsrBatchResult) * (size_t)batch))
+      ensure_bsum(c, 256) ||
+      c->part.ensure(c->stream, sizeof(CsrBatchResult) * (size_t)batch))
     return -1;
-  auto slot = [&](int i) {
-    return reinterpret_cast<T*>((char*)c->d_vec + (size_t)i * c->vec_bytes);
-  };
-  T* s_buf[2] = { slot(0), slot(1) };
-  T* vb[2] = { slot(2), slot(3) };
-  T* d_x = slot(4);
-  T* d_v = d_v_out ? d_v_out : slot(5);
-  CsrBatchResult* d_res = static_cast<CsrBatchResult*>(c->d_part);
+  T* s_buf[2] = { c->vec_slot<T>(0), c->vec_slot<T>(1) };
+  T* vb[2] = { c->vec_slot<T>(2), c->vec_slot<T>(3) };
+  T* d_x = c->vec_slot<T>(4);
+  T* d_v = d_v_out ? d_v_out : c->vec_slot<T>(5);
+  CsrBatchResult* d_res = static_cast<CsrBatchResult*>(c->part.p);
   hipStream_t s = c->stream;
-  const uint32_t per_check = o.batch ? o.batch : kDefaultBatch;
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)batch, s));
+  ST_CHECK(hipMemsetAsync(c->bstate.p, 0, sizeof(st_state) * (size_t)batch, s));
   ST_CHECK(hipMemsetAsync(c->d_bcount, 0, sizeof(uint32_t), s));
   if (launch_fill<T>(vb[0], h->n, (T)1, s))
     return -1;
   if (launch_csrb_rowsum(h, s_buf[0], s)) // K0
     return -1;
-  uint32_t enqueued = 0, cur = 0, batch_no = 0;
-  bool done = false;
-  while (!done && enqueued < o.max_itr) {
-    const uint32_t b = (o.max_itr - enqueued) < per_check ? (o.max_itr - enqueued)
-                                                          : per_check;
-    for (uint32_t j = 0; j < b; j++) {
-      const uint32_t k = enqueued + j; // launch k+1 evaluates round k
-      if (launch_csrb_round(h, s_buf[cur], s_buf[cur ^ 1], vb[k & 1],
-                            vb[(k + 1) & 1], d_x, o.eps, k + 1, o.max_itr,
-                            o.semantics, c->d_bstate, c->d_bcount, s))
-        return -1;
-      cur ^= 1;
-    }
-    enqueued += b;
-    const int sl = batch_no & 1;
-    if (launch_count_mirror(c->d_bcount, &c->h_bcount[sl], s))
-      return -1;
-    ST_CHECK(hipEventRecord(c->ev_flag[sl], s));
-    // wait for the previous batch's count while this batch runs
-    if (batch_no > 0) {
-      ST_CHECK(hipEventSynchronize(c->ev_flag[sl ^ 1]));
-      done = c->h_bcount[sl ^ 1] >= batch;
-    }
-    batch_no++;
-  }
-  if (launch_csrb_collect(h, vb[0], vb[1], d_v, c->d_bstate, d_res, s))
+  const int64_t enqueued = counted_rounds(
+    c, o.batch ? o.batch : kDefaultBatch, o.max_itr, batch,
+    [&](uint32_t k) { // launch k+1 evaluates round k
+      return launch_csrb_round(h, s_buf[k & 1], s_buf[(k + 1) & 1], vb[k & 1],
+                               vb[(k + 1) & 1], d_x, o.eps, k + 1, o.max_itr, o.semantics,
+                               c->d_bstate(), c->d_bcount, s);
+    });
+  if (enqueued < 0)
+    return -1;
+  if (launch_csrb_collect(h, vb[0], vb[1], d_v, c->d_bstate(), d_res, s))
     return -1;
   ST_CHECK(hipStreamSynchronize(s));
   std::vector<CsrBatchResult> res(batch);
   ST_CHECK(hipMemcpy(res.data(), d_res, sizeof(CsrBatchResult) * (size_t)batch,
                      hipMemcpyDeviceToHost));
   const double loop_ms = ms_since(t0);
-
-  const auto t1 = std::chrono::steady_clock::now();
-  uint32_t rounds = 0, all = 1;
-  for (uint32_t b = 0; b < batch; b++) {
-    const CsrBatchResult& fin = res[b];
-    ST_REQUIRE(fin.done, "internal: matrix %u ended without done flag", b);
-    eigen_vals[b] = (T)fin.lambda;
-    iter_cnts[b] = fin.iters;
-    if (converged)
-      converged[b] = fin.stop;
-    rounds = fin.end > rounds ? fin.end : rounds;
-    all &= fin.stop;
-  }
-  if (v_host)
-    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
-  const double d2h_ms = ms_since(t1);
-  if (stats) {
+  if (stats)
     std::memset(stats, 0, sizeof(*stats));
-    stats->loop_ms = loop_ms;
-    stats->d2h_ms = d2h_ms;
-    stats->rounds = rounds;
-    stats->converged = all;
-    stats->fused_launches = enqueued;
-  }
-  return (int64_t)loop_ms;
+  return report_entries<T>(res.data(), batch, "matrix", eigen_vals, iter_cnts, converged,
+                           v_host, d_v, v_bytes, loop_ms, (uint32_t)enqueued, stats);
 }
 
 int64_t
@@ -1507,39 +1550,24 @@ solve_host_csr_batched(Context* c, int dtype, uint32_t batch,
   if (ensure_device(c))
     return -1;
   const uint32_t n = mat_first[batch];
-  const size_t elem = dtype ? 8 : 4;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
-               b_col = up(4 * nnz);
-  if (ensure_matrix(c, b_ptr + b_val + b_col))
+  const CsrSlots sl = csr_slots(dtype, n, nnz);
+  if (c->mat.ensure(c->stream, sl.bytes()))
     return -1;
-  char* base = static_cast<char*>(c->d_mat);
-  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
-  void* d_val = base + b_ptr;
-  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  char* base = static_cast<char*>(c->mat.p);
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
-                          hipMemcpyHostToDevice, c->stream));
-  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
-                          c->stream));
+  if (csr_copy_in(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals))
+    return -1;
   ST_CHECK(hipStreamSynchronize(c->stream));
   CsrBatchHandle* h = nullptr;
-  if (csr_batch_create(dtype, batch, mat_first, nnz, d_ptr, d_col, d_val,
-                       c->stream, &h))
+  if (csr_batch_create(dtype, batch, mat_first, nnz, sl.ptr(base), sl.col(base),
+                       sl.val(base), c->stream, &h))
     return -1;
   const double h2d = ms_since(t0);
   st_stats local{};
   const int64_t rc = solve_csr_batched(c, h, nullptr, eigen_vecs, eigen_vals,
                                        iter_cnts, converged, opt, &local);
   (void)csr_batch_destroy(h);
-  if (rc < 0)
-    return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return rc < 0 ? -1 : finish_twin(local, h2d, stats);
 }
 
 // The solve of up to 8 operators A + sum_j u_{c,j} w_{c,j}^T on one matrix
@@ -1558,88 +1586,48 @@ solve_csr_multi_t(Context* c, const CsrHandle* h, const CsrMultiHandle* t, T* d_
   const uint32_t C = t->C;
   const size_t out_bytes = sizeof(T) * (size_t)h->n * C;
   if (ensure_device(c) || ensure_bstate(c, C) || ensure_bsum(c, 256) ||
-      ensure_part(c, sizeof(CsrBatchResult) * (size_t)C))
+      c->part.ensure(c->stream, sizeof(CsrBatchResult) * (size_t)C))
     return -1;
-  struct Freed
+  DeviceBuf tmp_out; // host output only: the collected [C][n] lives for this call
+  struct Release
   {
-    void* p = nullptr;
-    ~Freed()
-    {
-      if (p)
-        (void)hipFree(p);
-    }
-  } tmp_out; // host output only: the collected [C][n] lives for this call
+    DeviceBuf& b;
+    ~Release() { b.release(); }
+  } release_tmp{ tmp_out };
+  hipStream_t s = c->stream;
   if (!d_v_out) {
-    ST_CHECK(hipMalloc(&tmp_out.p, out_bytes));
+    if (tmp_out.ensure(s, out_bytes))
+      return -1;
     d_v_out = static_cast<T*>(tmp_out.p);
   }
-  CsrBatchResult* d_res = static_cast<CsrBatchResult*>(c->d_part);
-  hipStream_t s = c->stream;
-  const uint32_t per_check = o.batch ? o.batch : kDefaultBatch;
+  CsrBatchResult* d_res = static_cast<CsrBatchResult*>(c->part.p);
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)C, s));
+  ST_CHECK(hipMemsetAsync(c->bstate.p, 0, sizeof(st_state) * (size_t)C, s));
   ST_CHECK(hipMemsetAsync(c->d_bcount, 0, sizeof(uint32_t), s));
   if (launch_fill<T>(static_cast<T*>(t->v[0]), (uint64_t)h->n * t->CP, (T)1, s))
     return -1;
   if (launch_csr_multi_rowsum(h, t, t->s[0], t->scratch, s)) // K0
     return -1;
-  uint32_t enqueued = 0, cur = 0, batch_no = 0;
-  bool done = false;
-  while (!done && enqueued < o.max_itr) {
-    const uint32_t b = (o.max_itr - enqueued) < per_check ? (o.max_itr - enqueued)
-                                                          : per_check;
-    for (uint32_t j = 0; j < b; j++) {
-      const uint32_t k = enqueued + j; // launch k+1 evaluates round k
-      if (launch_csr_multi_round(h, t, t->s[cur], t->s[cur ^ 1], t->v[k & 1],
-                                 t->v[(k + 1) & 1], t->scratch, o.eps, k + 1,
-                                 o.max_itr, o.semantics, c->d_bstate, c->d_bcount, s))
-        return -1;
-      cur ^= 1;
-    }
-    enqueued += b;
-    const int sl = batch_no & 1;
-    if (launch_count_mirror(c->d_bcount, &c->h_bcount[sl], s))
-      return -1;
-    ST_CHECK(hipEventRecord(c->ev_flag[sl], s));
-    // wait for the previous batch's count while this batch runs
-    if (batch_no > 0) {
-      ST_CHECK(hipEventSynchronize(c->ev_flag[sl ^ 1]));
-      done = c->h_bcount[sl ^ 1] >= C;
-    }
-    batch_no++;
-  }
-  if (launch_csr_multi_collect(t, t->v[0], t->v[1], d_v_out, c->d_bstate, d_res, s))
+  const int64_t enqueued = counted_rounds(
+    c, o.batch ? o.batch : kDefaultBatch, o.max_itr, C,
+    [&](uint32_t k) { // launch k+1 evaluates round k
+      return launch_csr_multi_round(h, t, t->s[k & 1], t->s[(k + 1) & 1], t->v[k & 1],
+                                    t->v[(k + 1) & 1], t->scratch, o.eps, k + 1, o.max_itr,
+                                    o.semantics, c->d_bstate(), c->d_bcount, s);
+    });
+  if (enqueued < 0)
+    return -1;
+  if (launch_csr_multi_collect(t, t->v[0], t->v[1], d_v_out, c->d_bstate(), d_res, s))
     return -1;
   ST_CHECK(hipStreamSynchronize(s));
   CsrBatchResult res[csr::kMultiMax];
   ST_CHECK(hipMemcpy(res, d_res, sizeof(CsrBatchResult) * (size_t)C,
                      hipMemcpyDeviceToHost));
   const double loop_ms = ms_since(t0);
-
-  const auto t1 = std::chrono::steady_clock::now();
-  uint32_t rounds = 0, all = 1;
-  for (uint32_t b = 0; b < C; b++) {
-    const CsrBatchResult& fin = res[b];
-    ST_REQUIRE(fin.done, "internal: column %u ended without done flag", b);
-    eigen_vals[b] = (T)fin.lambda;
-    iter_cnts[b] = fin.iters;
-    if (converged)
-      converged[b] = fin.stop;
-    rounds = fin.end > rounds ? fin.end : rounds;
-    all &= fin.stop;
-  }
-  if (v_host)
-    ST_CHECK(hipMemcpy(v_host, d_v_out, out_bytes, hipMemcpyDeviceToHost));
-  const double d2h_ms = ms_since(t1);
-  if (stats) {
+  if (stats)
     std::memset(stats, 0, sizeof(*stats));
-    stats->loop_ms = loop_ms;
-    stats->d2h_ms = d2h_ms;
-    stats->rounds = rounds;
-    stats->converged = all;
-    stats->fused_launches = enqueued;
-  }
-  return (int64_t)loop_ms;
+  return report_entries<T>(res, C, "column", eigen_vals, iter_cnts, converged, v_host,
+                           d_v_out, out_bytes, loop_ms, (uint32_t)enqueued, stats);
 }
 
 int
@@ -1750,26 +1738,13 @@ solve_host_csr_multi(Context* c, int dtype, uint32_t n, uint64_t nnz,
   ST_REQUIRE(c, "null queue");
   if (ensure_device(c))
     return -1;
-  const size_t elem = dtype ? 8 : 4;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_ptr = up(8 * ((size_t)n + 1)), b_val = up(elem * nnz),
-               b_col = up(4 * nnz);
-  if (ensure_matrix(c, b_ptr + b_val + b_col))
+  const CsrSlots sl = csr_slots(dtype, n, nnz);
+  if (c->mat.ensure(c->stream, sl.bytes()))
     return -1;
-  char* base = static_cast<char*>(c->d_mat);
-  int64_t* d_ptr = reinterpret_cast<int64_t*>(base);
-  void* d_val = base + b_ptr;
-  int32_t* d_col = reinterpret_cast<int32_t*>(base + b_ptr + b_val);
+  char* base = static_cast<char*>(c->mat.p);
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(d_ptr, row_ptr, 8 * ((size_t)n + 1),
-                          hipMemcpyHostToDevice, c->stream));
-  ST_CHECK(hipMemcpyAsync(d_val, vals, elem * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipMemcpyAsync(d_col, col_idx, 4 * nnz, hipMemcpyHostToDevice,
-                          c->stream));
-  ST_CHECK(hipStreamSynchronize(c->stream));
   CsrHandle* h = nullptr;
-  if (csr_create(dtype, n, nnz, d_ptr, d_col, d_val, c->stream, &h, flags))
+  if (csr_stage(c, sl, base, dtype, n, nnz, row_ptr, col_idx, vals, flags, &h))
     return -1;
   CsrMultiHandle* t = nullptr;
   if (csr_multi_create(h, C, K, nullptr, nullptr, c->stream, &t, pu.data(), pw.data())) {
@@ -1782,12 +1757,7 @@ solve_host_csr_multi(Context* c, int dtype, uint32_t n, uint64_t nnz,
                                      iter_cnts, converged, opt, &local);
   (void)csr_multi_destroy(t);
   (void)csr_destroy(h);
-  if (rc < 0)
-    return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return rc < 0 ? -1 : finish_twin(local, h2d, stats);
 }
 
 template <typename T>
@@ -1801,24 +1771,20 @@ solve_host(Context* c, const T* mat, uint32_t n, T* eigen_val, T* eigen_vec,
   if (ensure_device(c))
     return -1;
   const size_t bytes = sizeof(T) * (size_t)n * n;
-  if (ensure_matrix(c, bytes))
+  if (c->mat.ensure(c->stream, bytes))
     return -1;
   // the reference's timed region starts before the first kernel, which
   // performs the lazy host->device copy (similarity_transform.cpp:36-40)
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(c->d_mat, mat, bytes, hipMemcpyHostToDevice,
+  ST_CHECK(hipMemcpyAsync(c->mat.p, mat, bytes, hipMemcpyHostToDevice,
                           c->stream));
   ST_CHECK(hipStreamSynchronize(c->stream));
   const double h2d = ms_since(t0);
   st_stats local{};
-  if (solve_device<T>(c, reinterpret_cast<T*>(c->d_mat), n, nullptr,
-                      eigen_vec, eigen_val, iter_cnt, opt, &local,
-                      false) < 0)
+  if (solve_device<T>(c, Operator::dense(c->mat.p, n), nullptr, eigen_vec, eigen_val,
+                      iter_cnt, opt, &local, false) < 0)
     return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return finish_twin(local, h2d, stats);
 }
 
 // what both batched entry points reject before touching the device
@@ -1859,7 +1825,8 @@ batched_args(Context* c, uint32_t batch, uint32_t n, const st_options* opt,
 // row's sum does not depend on the rows around it).  Per host check
 // (opt->batch rounds, default 8) one word, the count of finished matrices,
 // is mirrored to pinned memory; the loop stops enqueuing once it reaches
-// `batch`.  The caller (solve_batched) has checked the arguments.
+// `batch`.  The caller (solve_batched) has checked the arguments and cleared
+// the stats.
 template <typename T>
 int64_t
 solve_batched_rounds(Context* c, T* d_mats, uint32_t batch, uint32_t n,
@@ -1869,14 +1836,11 @@ solve_batched_rounds(Context* c, T* d_mats, uint32_t batch, uint32_t n,
   const size_t v_bytes = sizeof(T) * (size_t)batch * n;
   if (ensure_device(c) || ensure_bstate(c, batch) || ensure_bsum(c, v_bytes))
     return -1;
-  T* s_buf[2] = { reinterpret_cast<T*>(c->d_bsum),
-                  reinterpret_cast<T*>((char*)c->d_bsum + c->bsum_bytes) };
-  T* d_v = d_v_out ? d_v_out
-                   : reinterpret_cast<T*>((char*)c->d_bsum + 2 * c->bsum_bytes);
+  T* s_buf[2] = { c->bsum_slot<T>(0), c->bsum_slot<T>(1) };
+  T* d_v = d_v_out ? d_v_out : c->bsum_slot<T>(2);
   hipStream_t s = c->stream;
-  const uint32_t per_check = o.batch ? o.batch : kDefaultBatch;
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)batch, s));
+  ST_CHECK(hipMemsetAsync(c->bstate.p, 0, sizeof(st_state) * (size_t)batch, s));
   ST_CHECK(hipMemsetAsync(c->d_bcount, 0, sizeof(uint32_t), s));
   if (launch_fill<T>(d_v, (uint64_t)batch * n, (T)1, s))
     return -1;
@@ -1889,59 +1853,16 @@ solve_batched_rounds(Context* c, T* d_mats, uint32_t batch, uint32_t n,
       return -1;
   }
   const T eps = (T)o.eps;
-  uint32_t enqueued = 0, cur = 0, batch_no = 0;
-  bool done = false;
-  while (!done && enqueued < o.max_itr) {
-    const uint32_t b = (o.max_itr - enqueued) < per_check ? (o.max_itr - enqueued)
-                                                          : per_check;
-    for (uint32_t j = 0; j < b; j++) {
-      if (launch_round_batched<T>(d_mats, s_buf[cur], s_buf[cur ^ 1], d_v, batch,
-                                  n, eps, enqueued + j, o.max_itr, o.semantics,
-                                  c->d_bstate, c->d_bcount, s))
-        return -1;
-      cur ^= 1;
-    }
-    enqueued += b;
-    const int slot = batch_no & 1;
-    if (launch_count_mirror(c->d_bcount, &c->h_bcount[slot], s))
-      return -1;
-    ST_CHECK(hipEventRecord(c->ev_flag[slot], s));
-    // wait for the previous batch's count while this batch runs
-    if (batch_no > 0) {
-      ST_CHECK(hipEventSynchronize(c->ev_flag[slot ^ 1]));
-      done = c->h_bcount[slot ^ 1] >= batch;
-    }
-    batch_no++;
-  }
-  ST_CHECK(hipStreamSynchronize(s));
-  c->h_bstate.resize(batch);
-  ST_CHECK(hipMemcpy(c->h_bstate.data(), c->d_bstate,
-                     sizeof(st_state) * (size_t)batch, hipMemcpyDeviceToHost));
-  const double loop_ms = ms_since(t0);
-
-  const auto t1 = std::chrono::steady_clock::now();
-  uint32_t rounds = 0, all = 1;
-  for (uint32_t b = 0; b < batch; b++) {
-    const st_state& fin = c->h_bstate[b];
-    ST_REQUIRE(fin.done, "internal: matrix %u ended without done flag", b);
-    eigen_vals[b] = (T)fin.lambda;
-    iter_cnts[b] = fin.iters;
-    if (converged)
-      converged[b] = fin.stop;
-    rounds = fin.end > rounds ? fin.end : rounds;
-    all &= fin.stop;
-  }
-  if (v_host)
-    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
-  const double d2h_ms = ms_since(t1);
-  if (stats) {
-    stats->loop_ms = loop_ms;
-    stats->d2h_ms = d2h_ms;
-    stats->rounds = rounds;
-    stats->converged = all;
-    stats->fused_launches = enqueued;
-  }
-  return (int64_t)loop_ms;
+  const int64_t enqueued = counted_rounds(
+    c, o.batch ? o.batch : kDefaultBatch, o.max_itr, batch, [&](uint32_t k) {
+      return launch_round_batched<T>(d_mats, s_buf[k & 1], s_buf[(k + 1) & 1], d_v, batch,
+                                     n, eps, k, o.max_itr, o.semantics, c->d_bstate(),
+                                     c->d_bcount, s);
+    });
+  if (enqueued < 0)
+    return -1;
+  return report_bstates<T>(c, batch, eigen_vals, iter_cnts, converged, v_host, d_v,
+                           v_bytes, t0, (uint32_t)enqueued, stats);
 }
 
 // Many small solves in one launch (k_solve_batched: a workgroup per matrix
@@ -1971,43 +1892,17 @@ solve_batched(Context* c, T* d_mats, uint32_t batch, uint32_t n, T* d_v_out,
                                    eigen_vals, iter_cnts, converged, o, stats);
   const size_t v_bytes = sizeof(T) * (size_t)batch * n;
   if (ensure_device(c) || ensure_bstate(c, batch) ||
-      (!d_v_out && ensure_part(c, v_bytes))) // d_part: free outside flat rounds
+      (!d_v_out && c->part.ensure(c->stream, v_bytes))) // part: free outside flat rounds
     return -1;
-  T* d_v = d_v_out ? d_v_out : reinterpret_cast<T*>(c->d_part);
+  T* d_v = d_v_out ? d_v_out : reinterpret_cast<T*>(c->part.p);
   hipStream_t s = c->stream;
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)batch, s));
+  ST_CHECK(hipMemsetAsync(c->bstate.p, 0, sizeof(st_state) * (size_t)batch, s));
   if (launch_solve_batched<T>(d_mats, d_v, batch, n, (T)o.eps, o.max_itr,
-                              o.semantics, c->d_bstate, s))
+                              o.semantics, c->d_bstate(), s))
     return -1;
-  ST_CHECK(hipStreamSynchronize(s));
-  c->h_bstate.resize(batch);
-  ST_CHECK(hipMemcpy(c->h_bstate.data(), c->d_bstate,
-                     sizeof(st_state) * (size_t)batch, hipMemcpyDeviceToHost));
-  const double loop_ms = ms_since(t0);
-
-  const auto t1 = std::chrono::steady_clock::now();
-  uint32_t rounds = 0, all = 1;
-  for (uint32_t b = 0; b < batch; b++) {
-    const st_state& fin = c->h_bstate[b];
-    ST_REQUIRE(fin.done, "internal: matrix %u ended without done flag", b);
-    eigen_vals[b] = (T)fin.lambda;
-    iter_cnts[b] = fin.iters;
-    if (converged)
-      converged[b] = fin.stop;
-    rounds = fin.end > rounds ? fin.end : rounds;
-    all &= fin.stop;
-  }
-  if (v_host)
-    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
-  const double d2h_ms = ms_since(t1);
-  if (stats) {
-    stats->loop_ms = loop_ms;
-    stats->d2h_ms = d2h_ms;
-    stats->rounds = rounds;
-    stats->converged = all;
-  }
-  return (int64_t)loop_ms;
+  return report_bstates<T>(c, batch, eigen_vals, iter_cnts, converged, v_host, d_v,
+                           v_bytes, t0, 0, stats);
 }
 
 // host-pointer twin: [mats | v] staged in the context's matrix buffer
@@ -2024,26 +1919,22 @@ solve_batched_host(Context* c, const T* mats, uint32_t batch, uint32_t n,
     return solve_batched<T>(c, nullptr, 0, n, nullptr, nullptr, nullptr,
                             nullptr, nullptr, opt, stats);
   ST_REQUIRE(mats && eigen_vals && eigen_vecs && iter_cnts, "null pointer");
-  const size_t bytes =
-    (sizeof(T) * (size_t)batch * n * n + 255) & ~(size_t)255; // v stays aligned
+  const size_t bytes = up256(sizeof(T) * (size_t)batch * n * n); // v stays aligned
   if (ensure_device(c) ||
-      ensure_matrix(c, bytes + sizeof(T) * (size_t)batch * n))
+      c->mat.ensure(c->stream, bytes + sizeof(T) * (size_t)batch * n))
     return -1;
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(c->d_mat, mats, sizeof(T) * (size_t)batch * n * n,
+  ST_CHECK(hipMemcpyAsync(c->mat.p, mats, sizeof(T) * (size_t)batch * n * n,
                           hipMemcpyHostToDevice, c->stream));
   ST_CHECK(hipStreamSynchronize(c->stream));
   const double h2d = ms_since(t0);
-  T* d_mats = reinterpret_cast<T*>(c->d_mat);
-  T* d_v = reinterpret_cast<T*>((char*)c->d_mat + bytes);
+  T* d_mats = reinterpret_cast<T*>(c->mat.p);
+  T* d_v = reinterpret_cast<T*>((char*)c->mat.p + bytes);
   st_stats local{};
   if (solve_batched<T>(c, d_mats, batch, n, d_v, eigen_vecs, eigen_vals,
                        iter_cnts, nullptr, opt, &local) < 0)
     return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return finish_twin(local, h2d, stats);
 }
 
 // The size-class plan of a variable-size batch (pure host code): a stable
@@ -2134,9 +2025,9 @@ solve_vbatched(Context* c, T* const* mat_ptrs, const uint32_t* dims,
     v_elems += dims[b];
   const size_t v_bytes = sizeof(T) * v_elems;
   if (ensure_device(c) || ensure_bstate(c, batch) || ensure_vbatch(c, batch) ||
-      (!d_v_out && ensure_part(c, v_bytes))) // d_part: free outside flat rounds
+      (!d_v_out && c->part.ensure(c->stream, v_bytes))) // part: free outside flat rounds
     return -1;
-  T* d_v = d_v_out ? d_v_out : reinterpret_cast<T*>(c->d_part);
+  T* d_v = d_v_out ? d_v_out : reinterpret_cast<T*>(c->part.p);
   hipStream_t s = c->stream;
   const auto t0 = std::chrono::steady_clock::now();
   // the table in plan order: entry j describes matrix order[j] (the
@@ -2156,47 +2047,20 @@ solve_vbatched(Context* c, T* const* mat_ptrs, const uint32_t* dims,
   ST_CHECK(hipMemcpyAsync(c->d_vb, c->h_vb, vb_bytes(batch),
                           hipMemcpyHostToDevice, s));
   const VBatchDesc* d_desc = reinterpret_cast<const VBatchDesc*>(c->d_vb);
-  ST_CHECK(hipMemsetAsync(c->d_bstate, 0, sizeof(st_state) * (size_t)batch, s));
+  ST_CHECK(hipMemsetAsync(c->bstate.p, 0, sizeof(st_state) * (size_t)batch, s));
   uint32_t launches = 0;
   for (uint32_t k = kSolveShapeClasses; k-- > 0;) {
     const uint32_t count = class_first[k + 1] - class_first[k];
     if (!count)
       continue;
     if (launch_solve_vbatched<T>(d_desc, class_first[k], count, k, d_v,
-                                 (T)o.eps, o.max_itr, o.semantics, c->d_bstate,
+                                 (T)o.eps, o.max_itr, o.semantics, c->d_bstate(),
                                  s))
       return -1;
     launches++;
   }
-  ST_CHECK(hipStreamSynchronize(s));
-  c->h_bstate.resize(batch);
-  ST_CHECK(hipMemcpy(c->h_bstate.data(), c->d_bstate,
-                     sizeof(st_state) * (size_t)batch, hipMemcpyDeviceToHost));
-  const double loop_ms = ms_since(t0);
-
-  const auto t1 = std::chrono::steady_clock::now();
-  uint32_t rounds = 0, all = 1;
-  for (uint32_t b = 0; b < batch; b++) {
-    const st_state& fin = c->h_bstate[b];
-    ST_REQUIRE(fin.done, "internal: matrix %u ended without done flag", b);
-    eigen_vals[b] = (T)fin.lambda;
-    iter_cnts[b] = fin.iters;
-    if (converged)
-      converged[b] = fin.stop;
-    rounds = fin.end > rounds ? fin.end : rounds;
-    all &= fin.stop;
-  }
-  if (v_host)
-    ST_CHECK(hipMemcpy(v_host, d_v, v_bytes, hipMemcpyDeviceToHost));
-  const double d2h_ms = ms_since(t1);
-  if (stats) {
-    stats->loop_ms = loop_ms;
-    stats->d2h_ms = d2h_ms;
-    stats->rounds = rounds;
-    stats->converged = all;
-    stats->fused_launches = launches;
-  }
-  return (int64_t)loop_ms;
+  return report_bstates<T>(c, batch, eigen_vals, iter_cnts, converged, v_host, d_v,
+                           v_bytes, t0, launches, stats);
 }
 
 // host-pointer twin: [tightly packed mats | v] staged in the context's matrix
@@ -2228,11 +2092,11 @@ solve_vbatched_host(Context* c, const T* mats, const uint32_t* dims,
     m_elems += (size_t)dims[b] * dims[b];
     v_elems += dims[b];
   }
-  const size_t bytes = (sizeof(T) * m_elems + 255) & ~(size_t)255; // v stays aligned
-  if (ensure_device(c) || ensure_matrix(c, bytes + sizeof(T) * v_elems))
+  const size_t bytes = up256(sizeof(T) * m_elems); // v stays aligned
+  if (ensure_device(c) || c->mat.ensure(c->stream, bytes + sizeof(T) * v_elems))
     return -1;
-  T* d_mats = reinterpret_cast<T*>(c->d_mat);
-  T* d_v = reinterpret_cast<T*>((char*)c->d_mat + bytes);
+  T* d_mats = reinterpret_cast<T*>(c->mat.p);
+  T* d_v = reinterpret_cast<T*>((char*)c->mat.p + bytes);
   std::vector<T*> ptrs(batch);
   size_t off = 0;
   for (uint32_t b = 0; b < batch; b++) {
@@ -2240,7 +2104,7 @@ solve_vbatched_host(Context* c, const T* mats, const uint32_t* dims,
     off += (size_t)dims[b] * dims[b];
   }
   const auto t0 = std::chrono::steady_clock::now();
-  ST_CHECK(hipMemcpyAsync(c->d_mat, mats, sizeof(T) * m_elems,
+  ST_CHECK(hipMemcpyAsync(c->mat.p, mats, sizeof(T) * m_elems,
                           hipMemcpyHostToDevice, c->stream));
   ST_CHECK(hipStreamSynchronize(c->stream));
   const double h2d = ms_since(t0);
@@ -2248,10 +2112,7 @@ solve_vbatched_host(Context* c, const T* mats, const uint32_t* dims,
   if (solve_vbatched<T>(c, ptrs.data(), dims, batch, d_v, eigen_vecs,
                         eigen_vals, iter_cnts, nullptr, opt, &local) < 0)
     return -1;
-  local.h2d_ms = h2d;
-  if (stats)
-    *stats = local;
-  return (int64_t)(h2d + local.loop_ms);
+  return finish_twin(local, h2d, stats);
 }
 
 int
@@ -2503,30 +2364,14 @@ destroy_queue(void* wq)
   (void)hipSetDevice(c->device);
   if (c->stream)
     (void)hipStreamSynchronize(c->stream);
-  if (c->d_mat)
-    (void)hipFree(c->d_mat);
-  if (c->d_vec)
-    (void)hipFree(c->d_vec);
-  if (c->d_part)
-    (void)hipFree(c->d_part);
-  if (c->d_trace)
-    (void)hipFree(c->d_trace);
-  if (c->d_state)
-    (void)hipFree(c->d_state);
-  if (c->d_bstate)
-    (void)hipFree(c->d_bstate);
-  if (c->d_bsum)
-    (void)hipFree(c->d_bsum);
-  if (c->d_bcount)
-    (void)hipFree(c->d_bcount);
-  if (c->h_bcount)
-    (void)hipHostFree(c->h_bcount);
-  if (c->d_vb)
-    (void)hipFree(c->d_vb);
-  if (c->h_vb)
-    (void)hipHostFree(c->h_vb);
-  if (c->h_state)
-    (void)hipHostFree(c->h_state);
+  for (st::DeviceBuf* b : { &c->mat, &c->vec, &c->part, &c->trace, &c->bstate, &c->bsum })
+    b->release();
+  for (void* p : { (void*)c->d_state, (void*)c->d_bcount, c->d_vb })
+    if (p)
+      (void)hipFree(p);
+  for (void* p : { (void*)c->h_state, (void*)c->h_bcount, c->h_vb })
+    if (p)
+      (void)hipHostFree(p);
   for (hipEvent_t e : c->ev_flag)
     if (e)
       (void)hipEventDestroy(e);
@@ -2557,8 +2402,8 @@ st_last_round_sums(void* wq, void* sums, unsigned int cap_rounds)
   ST_REQUIRE(sums || cap_rounds == 0, "st_last_round_sums: null buffer");
   const uint32_t r = c->trace_rounds;
   if (r && cap_rounds) {
-    const size_t row = c->trace.size() / r;
-    std::memcpy(sums, c->trace.data(), row * (cap_rounds < r ? cap_rounds : r));
+    const size_t row = c->trace_sums.size() / r;
+    std::memcpy(sums, c->trace_sums.data(), row * (cap_rounds < r ? cap_rounds : r));
   }
   return (int)r;
 }
@@ -2633,9 +2478,9 @@ st_solve_device_f32(void* wq, float* d_mat, unsigned int dim,
 {
   st::clear_error();
   st::DeviceGuard guard;
-  return st::solve_device<float>(st::as_ctx(wq), d_mat, dim, d_eigen_vec,
-                                 eigen_vec_host, eigen_val, iter_cnt, opt,
-                                 stats);
+  return st::solve_device<float>(st::as_ctx(wq), st::Operator::dense(d_mat, dim),
+                                 d_eigen_vec, eigen_vec_host, eigen_val, iter_cnt,
+                                 opt, stats);
 }
 
 int64_t
@@ -3036,9 +2881,9 @@ st_solve_device_f64(void* wq, double* d_mat, unsigned int dim,
 {
   st::clear_error();
   st::DeviceGuard guard;
-  return st::solve_device<double>(st::as_ctx(wq), d_mat, dim, d_eigen_vec,
-                                  eigen_vec_host, eigen_val, iter_cnt, opt,
-                                  stats);
+  return st::solve_device<double>(st::as_ctx(wq), st::Operator::dense(d_mat, dim),
+                                  d_eigen_vec, eigen_vec_host, eigen_val, iter_cnt,
+                                  opt, stats);
 }
 
 int64_t
