@@ -11,13 +11,15 @@ SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hi
             eigen_value_amd/csrc/st_half.hip eigen_value_amd/csrc/st_csr.hip \
             eigen_value_amd/csrc/st_csr_batch.hip eigen_value_amd/csrc/st_csr_transpose.hip \
             eigen_value_amd/csrc/st_csr_terms.hip eigen_value_amd/csrc/st_csr_multi.hip \
-            eigen_value_amd/csrc/st_csr_product.hip eigen_value_amd/csrc/st_csr_pattern.hip
+            eigen_value_amd/csrc/st_csr_product.hip eigen_value_amd/csrc/st_csr_pattern.hip \
+            eigen_value_amd/csrc/st_left.hip
 OBJ     := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
-# st_kernels compiled to also export the launch-table setters of
+# st_kernels and st_left compiled to also export the launch-table setters of
 # include/st_tuning.h
-TUNING_OBJ := build/st_kernels_tuning.o $(filter-out build/st_kernels.o,$(OBJ))
+TUNING_OBJ := build/st_kernels_tuning.o build/st_left_tuning.o \
+              $(filter-out build/st_kernels.o build/st_left.o,$(OBJ))
 LIB_TUNING := eigen_value_amd/lib/libsimilarity_transform_tuning.so
 HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/csrc/st_internal.h \
             eigen_value_amd/csrc/st_device.h eigen_value_amd/csrc/st_rendezvous.h \
@@ -25,7 +27,8 @@ HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/c
             eigen_value_amd/csrc/st_csr_host.h eigen_value_amd/csrc/st_csr_batch.h \
             eigen_value_amd/csrc/st_csr_plan.h eigen_value_amd/csrc/st_csr_transpose.h \
             eigen_value_amd/csrc/st_csr_terms.h eigen_value_amd/csrc/st_csr_multi.h \
-            eigen_value_amd/csrc/st_csr_product.h eigen_value_amd/csrc/st_csr_pattern.h
+            eigen_value_amd/csrc/st_csr_product.h eigen_value_amd/csrc/st_csr_pattern.h \
+            eigen_value_amd/csrc/st_left.h eigen_value_amd/csrc/st_left_host.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 
@@ -33,7 +36,7 @@ build/%.o: eigen_value_amd/csrc/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/st_kernels_tuning.o: eigen_value_amd/csrc/st_kernels.hip $(HDRS)
+build/%_tuning.o: eigen_value_amd/csrc/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -DST_TUNING_ABI=1 -c $< -o $@
 
@@ -109,9 +112,19 @@ csr_pattern_sanitize: $(LIB) tests/cpp/csr_pattern_sanitize.cpp eigen_value_amd/
 	./build/csr_pattern_sanitize build/csr_tables/table0.bin build/csr_tables/table1.bin \
 	  build/csr_tables/table2.bin
 
+# the host arithmetic of the dense left-vector solve (st_left_host.h: rows
+# per block, scratch layout, launch grid, the host twin's staging) under the
+# host sanitizers: a stand-alone program, run on the CPU, that needs nothing
+left_sanitize: tests/cpp/left_sanitize.cpp eigen_value_amd/csrc/st_left_host.h
+	@mkdir -p build
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	  -fno-omit-frame-pointer -Ieigen_value_amd/csrc tests/cpp/left_sanitize.cpp \
+	  -o build/left_sanitize
+	./build/left_sanitize
+
 clean:
 	rm -rf build eigen_value_amd/lib
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean probe csr_terms_sanitize csr_multi_sanitize csr_product_sanitize \
-        csr_pattern_sanitize
+        csr_pattern_sanitize left_sanitize

@@ -306,6 +306,23 @@ def _declare(L: ctypes.CDLL) -> None:
     L.max_eigen_value_half_ex.restype = i64
     L.st_half_shape_desc.argtypes = []
     L.st_half_shape_desc.restype = ctypes.c_char_p
+    # dense left vector (the matrix read where it lies, swept by columns)
+    for sfx, T in (("f32", f32), ("f64", f64)):
+        getattr(L, f"st_solve_device_left_{sfx}").argtypes = [P, P, u32, P, P, P, P, P, P]
+        getattr(L, f"st_solve_device_left_{sfx}").restype = i64
+        getattr(L, f"st_colsum_{sfx}").argtypes = [P, P, P, u32, P]
+        getattr(L, f"st_colsum_{sfx}").restype = i32
+        getattr(L, f"st_mfree_left_round_{sfx}").argtypes = [P, P, P, P, P, P, u32, T, u32,
+                                                             u32, u32, P, P]
+        getattr(L, f"st_mfree_left_round_{sfx}").restype = i32
+    L.max_eigen_value_left_ex.argtypes = [P, i32, P, P, P, u32, P, P, P]
+    L.max_eigen_value_left_ex.restype = i64
+    L.st_left_shape.argtypes = [i32, u32, P, P]
+    L.st_left_shape.restype = i32
+    L.st_left_scratch.argtypes = [i32, u32]
+    L.st_left_scratch.restype = u64
+    L.st_left_shape_desc.argtypes = []
+    L.st_left_shape_desc.restype = ctypes.c_char_p
     # sparse (CSR) solve
     L.st_csr_class_limits.argtypes = [i32, P, P, i32]
     L.st_csr_class_limits.restype = i32
@@ -690,6 +707,21 @@ def csr_transpose_shape(L: Optional[ctypes.CDLL] = None) -> dict:
         k, v = item.split("=")
         out[k] = int(v) if v.isdigit() else v
     return out
+
+
+def left_shape(dtype_code: int, n: int, L: Optional[ctypes.CDLL] = None) -> dict:
+    """st_left_shape and st_left_shape_desc for one (dtype, n), no GPU: rows
+    (RB of the order contract), combine (0 serial, 1 tree), block, w (columns
+    per lane when the row stride allows 16-byte loads) and strip = block * w."""
+    L = L or load()
+    rows, comb = ctypes.c_uint32(), ctypes.c_uint32()
+    check(L.st_left_shape(dtype_code, n, ctypes.byref(rows), ctypes.byref(comb)),
+          "st_left_shape", L)
+    desc = dict(kv.split("=") for kv in L.st_left_shape_desc().decode().split())
+    block = int(desc["block"])
+    w = int(desc["bytes_per_load"]) // (8 if dtype_code == DTYPE_F64 else 4)
+    return {"rows": rows.value, "combine": comb.value, "block": block, "w": w,
+            "strip": block * w}
 
 
 def round_sums(L: ctypes.CDLL, q, n: int, dtype):

@@ -140,6 +140,21 @@ int launch_mfree_half(int storage, const void* a0, const float* s_prev,
                       st_state* st, hipStream_t stream);
 int launch_narrow(int storage, const float* in, void* out, uint64_t count,
                   hipStream_t stream);
+// the dense left-vector round (st_left.hip): launch 0 (the column sums) and
+// launch k >= 1 (k_csr_prep, k_left_sweep, k_left_finish) on an n x n matrix
+// that is only read.  x holds n elements, part left_part_elems(dtype, n);
+// the step-level scratch is [x (left_x_elems) | part].  left_rows is RB of
+// the order contract, a function of (dtype, n)
+uint32_t left_rows(int dtype, uint32_t n);
+size_t left_x_elems(uint32_t n);
+size_t left_part_elems(int dtype, uint32_t n);
+template <typename T>
+int launch_colsum(const T* a, T* s, T* part, uint32_t n, hipStream_t stream);
+template <typename T>
+int launch_left_round(const T* a, const T* s_prev, T* s_next, const T* v_prev,
+                      T* v_cur, T* x, T* part, uint32_t n, T eps, uint32_t k,
+                      uint32_t max_itr, uint32_t semantics, st_state* st,
+                      hipStream_t stream);
 // the sparse (CSR) solve (st_csr.hip): a validated matrix with its plan.
 // The three arrays stay the caller's; order is the handle's own.
 struct CsrHandle

@@ -18,8 +18,8 @@
 //     (launches after the stop round return at once)
 // What the loop works on is one Operator value: the dense matrix (transformed
 // in place as above, or only read with ST_FLAG_MATRIX_FREE), a 16-bit matrix,
-// a CSR handle, CSR plus terms, the product of two handles, or a pattern
-// handle with optional terms.  Every read-only kind runs the matrix-free
+// a CSR handle, CSR plus terms, the product of two handles, a pattern handle
+// with optional terms, or a dense matrix swept by columns (the left vector).  Every read-only kind runs the matrix-free
 // loop; op_rowsum and op_round are the only places that tell the kinds apart.
 // A batch of matrices runs k_solve_batched (one launch, a workgroup per
 // matrix) or, with ST_FLAG_BATCH_ROUNDS, this loop with every launch
@@ -48,6 +48,7 @@
 
 #include "st_csr_host.h"
 #include "st_internal.h"
+#include "st_left_host.h"
 
 namespace st {
 
@@ -299,10 +300,10 @@ resolve(const st_options* opt, Resolved* r)
 // the only way to make one, so no other combination of handles exists.
 struct Operator
 {
-  enum Kind { kDense, kHalf, kCsr, kCsrTerms, kProduct, kPattern };
+  enum Kind { kDense, kHalf, kCsr, kCsrTerms, kProduct, kPattern, kDenseLeft };
   Kind kind;
   uint32_t n;
-  void* mat;                   // kDense: n x n of the vectors' type; kHalf: 16-bit elements
+  void* mat;                   // kDense, kDenseLeft: n x n of the vectors' type; kHalf: 16-bit elements
   int storage;                 // kHalf: ST_STORE_F16 / ST_STORE_BF16
   const CsrHandle* a;          // kCsr, kCsrTerms; kProduct: the right factor
   const CsrHandle* b;          // kProduct: the left factor of B A
@@ -338,12 +339,20 @@ struct Operator
   {
     return { kPattern, p->n, nullptr, 0, nullptr, nullptr, t, p };
   }
+  // u A = lambda u on the dense matrix where it lies: the loop never writes
+  // through d_mat and makes no copy of it
+  static Operator dense_left(const void* d_mat, uint32_t n)
+  {
+    return { kDenseLeft, n, const_cast<void*>(d_mat), 0,
+             nullptr, nullptr, nullptr, nullptr };
+  }
   bool read_only() const { return kind != kDense; }
 };
 
 // the loop's buffers a read-only operator works in besides s and v: x (the
 // pattern's z) in the first slot of the deferred ring, the product's y in its
-// second, dots and partials (terms; the flat K0's partials) in the flat scratch
+// second, dots and partials (terms; the flat K0's partials; the left round's
+// row-block partials) in the flat scratch
 template <typename T>
 struct OpScratch
 {
@@ -359,6 +368,8 @@ int
 op_rowsum(const Operator& op, T* s0, const OpScratch<T>& w, bool flat, hipStream_t s)
 {
   switch (op.kind) {
+    case Operator::kDenseLeft: // the column sums
+      return launch_colsum<T>(static_cast<const T*>(op.mat), s0, w.part, op.n, s);
     case Operator::kPattern:
       return launch_csr_pattern_rowsum(op.pat, op.terms, s0, w.part, s);
     case Operator::kProduct:
@@ -389,6 +400,10 @@ op_round(const Operator& op, const T* s_prev, T* s_next, const T* v_prev, T* v_c
          hipStream_t s)
 {
   switch (op.kind) {
+    case Operator::kDenseLeft:
+      return launch_left_round<T>(static_cast<const T*>(op.mat), s_prev, s_next, v_prev,
+                                  v_cur, w.x, w.part, op.n, (T)o.eps, launch, o.max_itr,
+                                  o.semantics, st, s);
     case Operator::kPattern:
       return launch_csr_pattern_round(op.pat, op.terms, s_prev, s_next, v_prev, v_cur, w.x,
                                       w.part, o.eps, launch, o.max_itr, o.semantics, st, s);
@@ -429,7 +444,8 @@ solve_device(Context* c, const Operator& op, T* d_v_out, T* v_host, T* eigen_val
   const uint32_t n = op.n;
   T* const d_mat = static_cast<T*>(op.mat); // kDense only
   ST_REQUIRE(c, "null queue");
-  if (op.kind == Operator::kDense || op.kind == Operator::kHalf)
+  if (op.kind == Operator::kDense || op.kind == Operator::kHalf ||
+      op.kind == Operator::kDenseLeft)
     ST_REQUIRE(op.mat, "null matrix");
   ST_REQUIRE(n > 0, "dim must be > 0");
   ST_REQUIRE(eigen_val && iter_cnt, "null output pointer");
@@ -477,6 +493,9 @@ solve_device(Context* c, const Operator& op, T* d_v_out, T* v_host, T* eigen_val
   if (flat_k0 && c->part.ensure(s, sizeof(T) * round_flat_scratch(n, n)))
     return -1;
   if (op.terms && c->part.ensure(s, csr_terms_dots_bytes(op.terms->K)))
+    return -1;
+  if (op.kind == Operator::kDenseLeft &&
+      c->part.ensure(s, sizeof(T) * left_part_elems(sizeof(T) == 8, n)))
     return -1;
   T* d_part = reinterpret_cast<T*>(c->part.p);
   // (the deferred ring is the dense loop's: free in every read-only one)
@@ -718,6 +737,75 @@ solve_device_half(Context* c, int storage, const void* d_mat, uint32_t n,
   ST_REQUIRE(((uintptr_t)d_mat & 1u) == 0, "half solve: matrix not 2-byte aligned");
   return solve_device<float>(c, Operator::half(storage, d_mat, n), d_v_out, v_host,
                              eigen_val, iter_cnt, opt, stats);
+}
+
+// The LEFT Perron vector of a device-resident dense matrix (u A = lambda u):
+// solve_device's matrix-free loop with the column-sum launchers (st_left.hip).
+// The matrix is only read and never copied.  Everything is checked before
+// anything is enqueued.
+int
+left_check_flags(const st_options* opt)
+{
+  const uint32_t flags = opt ? opt->flags : 0u;
+  constexpr uint32_t kNoLeft =
+    ST_FLAG_ROUND_LOOP | ST_FLAG_WRITE_EVERY_ROUND | ST_FLAG_BATCH_ROUNDS;
+  ST_REQUIRE((flags & kNoLeft) == 0,
+             "dense left solve: ST_FLAG_ROUND_LOOP, ST_FLAG_WRITE_EVERY_ROUND and "
+             "ST_FLAG_BATCH_ROUNDS are not supported (flags = %u): the matrix "
+             "is read only and every round is the same three launches", flags);
+  return 0;
+}
+
+template <typename T>
+int64_t
+solve_device_left(Context* c, const T* d_mat, uint32_t n, T* d_v_out, T* v_host,
+                  T* eigen_val, uint32_t* iter_cnt, const st_options* opt,
+                  st_stats* stats)
+{
+  if (left_check_flags(opt))
+    return -1;
+  ST_REQUIRE(d_mat, "dense left solve: null matrix");
+  ST_REQUIRE(n > 0, "dense left solve: dim must be > 0");
+  ST_REQUIRE(((uintptr_t)d_mat & (sizeof(T) - 1)) == 0,
+             "dense left solve: matrix not aligned to its element size");
+  return solve_device<T>(c, Operator::dense_left(d_mat, n), d_v_out, v_host, eigen_val,
+                         iter_cnt, opt, stats);
+}
+
+// the host twin: the workspace holds the matrix as the caller has it (one
+// slot, copied in once and only read)
+template <typename T>
+int64_t
+solve_host_left(Context* c, const T* mat, uint32_t n, T* eigen_val, T* eigen_vec,
+                uint32_t* iter_cnt, const st_options* opt, st_stats* stats)
+{
+  if (left_check_flags(opt))
+    return -1;
+  {
+    Resolved o;
+    if (resolve<T>(opt, &o))
+      return -1;
+  }
+  ST_REQUIRE(mat, "max_eigen_value_left_ex: null matrix");
+  ST_REQUIRE(n > 0, "max_eigen_value_left_ex: dim must be > 0");
+  ST_REQUIRE(eigen_val && eigen_vec && iter_cnt, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  ST_REQUIRE(n <= left::kNMax && left::stage_fits(n, sizeof(T)),
+             "max_eigen_value_left_ex: dim = %u is too large", n);
+  if (c->mat.ensure(c->stream, (size_t)left::stage_bytes(n, sizeof(T))))
+    return -1;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(c->mat.p, mat, sizeof(T) * (size_t)n * n, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  if (solve_device_left<T>(c, static_cast<const T*>(c->mat.p), n, nullptr, eigen_vec,
+                           eigen_val, iter_cnt, opt, &local) < 0)
+    return -1;
+  return finish_twin(local, h2d, stats);
 }
 
 int64_t
@@ -2481,6 +2569,47 @@ st_solve_device_f32(void* wq, float* d_mat, unsigned int dim,
   return st::solve_device<float>(st::as_ctx(wq), st::Operator::dense(d_mat, dim),
                                  d_eigen_vec, eigen_vec_host, eigen_val, iter_cnt,
                                  opt, stats);
+}
+
+int64_t
+st_solve_device_left_f32(void* wq, const float* d_mat, unsigned int dim,
+                         float* d_eigen_vec, float* eigen_vec_host, float* eigen_val,
+                         unsigned int* iter_cnt, const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_device_left<float>(st::as_ctx(wq), d_mat, dim, d_eigen_vec,
+                                      eigen_vec_host, eigen_val, iter_cnt, opt, stats);
+}
+
+int64_t
+st_solve_device_left_f64(void* wq, const double* d_mat, unsigned int dim,
+                         double* d_eigen_vec, double* eigen_vec_host, double* eigen_val,
+                         unsigned int* iter_cnt, const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  return st::solve_device_left<double>(st::as_ctx(wq), d_mat, dim, d_eigen_vec,
+                                       eigen_vec_host, eigen_val, iter_cnt, opt, stats);
+}
+
+int64_t
+max_eigen_value_left_ex(void* wq, int dtype, const void* mat, void* eigen_val,
+                        void* eigen_vec, unsigned int dim, unsigned int* iter_cnt,
+                        const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (dtype == 0)
+    return st::solve_host_left<float>(st::as_ctx(wq), (const float*)mat, dim,
+                                      (float*)eigen_val, (float*)eigen_vec, iter_cnt,
+                                      opt, stats);
+  if (dtype == 1)
+    return st::solve_host_left<double>(st::as_ctx(wq), (const double*)mat, dim,
+                                       (double*)eigen_val, (double*)eigen_vec, iter_cnt,
+                                       opt, stats);
+  st::set_error("max_eigen_value_left_ex: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  return -1;
 }
 
 int64_t

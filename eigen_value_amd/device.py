@@ -185,6 +185,59 @@ def mfree_round_flat(mat0, s_prev, s_next, v_prev, v_cur, part, state, row0: int
         "mfree_round_flat")
 
 
+def _dtype_code(dtype) -> int:
+    torch = _torch()
+    if dtype == torch.float64:
+        return _lib.DTYPE_F64
+    if dtype == torch.float32:
+        return _lib.DTYPE_F32
+    raise TypeError(f"float32/float64 required, got {dtype}")
+
+
+def left_scratch(n: int, dtype, device="cuda"):
+    """The scratch of ``colsum`` / ``mfree_left_round`` for an n x n matrix
+    (``st_left_scratch`` elements: x, then the row-block partials)."""
+    torch = _torch()
+    count = int(_lib.load().st_left_scratch(_dtype_code(dtype), n))
+    if count == 0:
+        raise _lib.EigenValueError(f"st_left_scratch: {_lib.last_error()}")
+    return torch.empty(count, dtype=dtype, device=device)
+
+
+def colsum(mat, out=None):
+    """s[c] = Σ_r A[r][c] for the columns of the square ``mat``, read where it
+    lies (``st_colsum_*``: launch 0 of the left-vector solve), in the order
+    ``st_left_shape`` publishes."""
+    _check_cuda(mat, out)
+    assert mat.is_contiguous() and mat.dim() == 2 and mat.shape[0] == mat.shape[1]
+    n = mat.shape[0]
+    if out is None:
+        out = mat.new_empty(n)
+    assert out.numel() >= n
+    scratch = left_scratch(n, mat.dtype, mat.device)
+    _lib.check(getattr(_lib.load(), f"st_colsum_{_sfx(mat)}")(
+        _ptr(mat), _ptr(out), _ptr(scratch), n, _stream(mat.device)), "colsum")
+    return out
+
+
+def mfree_left_round(mat0, s_prev, s_next, v_prev, v_cur, scratch, state, *,
+                     eps: float = 1e-3, k: int = 1, max_itr: int = _lib.ST_MAX_ITR,
+                     semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Launch k >= 1 of the left-vector solve (``st_mfree_left_round_*``):
+    round k-1's stats and v_{k-1} from s_prev exactly as ``mfree_round``, and
+    s_k[c] = (Σ_r A_0[r][c] x[r]) / x[c]; ``scratch`` is ``left_scratch``
+    (x stands at its start afterwards).  ``mat0`` is only read."""
+    _check_cuda(mat0, s_prev, s_next, v_prev, v_cur, scratch, state)
+    assert mat0.is_contiguous() and mat0.dim() == 2 and mat0.shape[0] == mat0.shape[1]
+    n = mat0.shape[0]
+    assert min(s_prev.numel(), s_next.numel(), v_prev.numel(), v_cur.numel()) >= n
+    assert scratch.dtype == mat0.dtype
+    assert scratch.numel() >= int(_lib.load().st_left_scratch(_dtype_code(mat0.dtype), n))
+    _lib.check(getattr(_lib.load(), f"st_mfree_left_round_{_sfx(mat0)}")(
+        _ptr(mat0), _ptr(s_prev), _ptr(s_next), _ptr(v_prev), _ptr(v_cur), _ptr(scratch), n,
+        eps, k, max_itr, semantics, _ptr(state), _stream(mat0.device)), "mfree_left_round")
+
+
 def _storage(t) -> int:
     """The storage code of a float16 / bfloat16 tensor (ST_STORE_*)."""
     torch = _torch()
@@ -1351,7 +1404,7 @@ class DeviceSolver:
               max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,
               time_kernels: bool = False, matrix_free: bool = False,
               round_loop: bool = False, write_every_round: bool = False,
-              trace_sums: bool = False):
+              trace_sums: bool = False, left: bool = False):
         """Returns (λ: float, v: tensor, iterations: int, stats: dict).
 
         Matrices of n <= 128 (fp64) / 256 (fp32) run the whole solve in one
@@ -1372,10 +1425,36 @@ class DeviceSolver:
         input is never written, so no copy is made.  ``mat`` may be a torch
         tensor or any DLPack producer (``__dlpack__``) on this device.
         ``trace_sums`` records every evaluated round's row sums
-        (``ST_FLAG_TRACE_SUMS``; identical results): ``last_round_sums()``."""
+        (``ST_FLAG_TRACE_SUMS``; identical results): ``last_round_sums()``.
+
+        ``left=True`` returns the LEFT Perron vector, ``v A = λ v``
+        (``st_solve_device_left_*``: the stationary distribution of a
+        row-stochastic ``mat`` is ``v / v.sum()``).  It implies the read-only
+        form: ``mat`` is swept by columns where it lies, never written and
+        never cloned, and no transposed copy is made; ``inplace``,
+        ``round_loop`` and ``write_every_round`` are ``ValueError``s with it,
+        16-bit tensors a ``TypeError``.  A non-contiguous ``mat`` whose
+        transpose is contiguous (``B.T`` of a row-major ``B``) IS ``Aᵀ``
+        stored row-major: the ordinary matrix-free solve then runs on that
+        storage, bit for bit ``solve(B, matrix_free=True)``, again without a
+        copy.  Any other non-contiguous layout is solved as its contiguous
+        copy.  ``last_round_sums()`` gives the column sums after
+        ``trace_sums``."""
         torch = _torch()
         if not isinstance(mat, torch.Tensor) and hasattr(mat, "__dlpack__"):
             mat = torch.from_dlpack(mat)   # any DLPack producer, zero copy
+        if not isinstance(left, bool):
+            raise TypeError(f"left must be a bool, got {type(left).__name__}")
+        if left:
+            if inplace:
+                raise ValueError("left=True reads the matrix only: inplace=True cannot be "
+                                 "combined with it")
+            if round_loop or write_every_round:
+                raise ValueError("left=True: round_loop and write_every_round belong to the "
+                                 "forms that write the matrix")
+            if mat.dtype in (torch.float16, torch.bfloat16):
+                raise TypeError("left=True needs a float32 / float64 matrix: the 16-bit "
+                                f"solve (solve_half) has no left form, got {mat.dtype}")
         _check_cuda(mat)
         if mat.device.index != (self.device.index if self.device.index is not None
                                 else torch.cuda.current_device()):
@@ -1384,8 +1463,15 @@ class DeviceSolver:
         assert mat.dim() == 2 and mat.shape == (n, n), "must be square"
         if inplace and not mat.is_contiguous():
             raise ValueError("inplace needs a contiguous (row-major) matrix")
-        work = mat if (inplace or matrix_free) else mat.clone()
-        work = work.contiguous()
+        entry = "st_solve_device"
+        if left and not mat.is_contiguous() and mat.t().is_contiguous():
+            # Aᵀ stored row-major: its right vector is A's left one
+            work, matrix_free = mat.t(), True
+        elif left:
+            work, matrix_free, entry = mat.contiguous(), True, "st_solve_device_left"
+        else:
+            work = mat if (inplace or matrix_free) else mat.clone()
+            work = work.contiguous()
         v = torch.empty(n, dtype=mat.dtype, device=mat.device)
         ev = (ctypes.c_double if mat.dtype == torch.float64 else ctypes.c_float)()
         it = ctypes.c_uint32()
@@ -1399,10 +1485,10 @@ class DeviceSolver:
         stats = _lib.st_stats()
         self._trace = (n, mat.dtype)
         _lib.check(self.L.st_set_stream(self.q, _stream(mat.device)), "st_set_stream")
-        rc = getattr(self.L, f"st_solve_device_{_sfx(mat)}")(
+        rc = getattr(self.L, f"{entry}_{_sfx(mat)}")(
             self.q, _ptr(work), n, _ptr(v), None, ctypes.byref(ev), ctypes.byref(it),
             ctypes.byref(opt), ctypes.byref(stats))
-        _lib.check(rc, "st_solve_device")
+        _lib.check(rc, entry)
         return float(ev.value), v, int(it.value), stats.as_dict()
 
     def solve_half(self, mat, *, eps: Optional[float] = None, max_itr: int = 0,

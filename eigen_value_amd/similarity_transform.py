@@ -113,6 +113,43 @@ class EigenValue:
         return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0]), stats.as_dict()
 
     # ------------------------------------------------------------------
+    def similarity_transform_left(self, mat: np.ndarray, *, eps: Optional[float] = None,
+                                  max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
+                                  batch: int = 0, time_kernels: bool = False,
+                                  trace_sums: bool = False):
+        """The LEFT Perron vector of a dense matrix, ``u A = λ u``
+        (``max_eigen_value_left_ex``): the matrix-free solve swept by columns
+        on the matrix as it is stored - no transposed copy on the host or on
+        the device.  For a row-stochastic matrix the stationary distribution
+        is ``u / u.sum()``.  ``trace_sums`` records every evaluated round's
+        COLUMN sums (``last_round_sums()``).
+
+        Returns ``(λ, u, ts_ms, iterations, stats_dict)`` in the dtype of
+        ``mat`` (float32 or float64)."""
+        m, n = mat.shape
+        assert m == n, "must be square matrix of floating points !"
+        mat = np.ascontiguousarray(mat)
+        if mat.dtype not in (np.float32, np.float64):
+            raise TypeError("float32 or float64 matrix required")
+        flags = ((_lib.ST_FLAG_TIME_KERNELS if time_kernels else 0)
+                 | _lib.ST_FLAG_MATRIX_FREE
+                 | (_lib.ST_FLAG_TRACE_SUMS if trace_sums else 0))
+        self._trace = (n, mat.dtype)
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, flags)
+        stats = _lib.st_stats()
+        eigen_val = np.empty(1, dtype=mat.dtype)
+        eigen_vec = np.empty(n, dtype=mat.dtype)
+        iter_cnt = np.zeros(1, dtype=np.uint32)
+        dtype = _lib.DTYPE_F32 if mat.dtype == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_left_ex(
+            self.sycl_q, dtype, mat.ctypes.data, eigen_val.ctypes.data,
+            eigen_vec.ctypes.data, n, iter_cnt.ctypes.data,
+            ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(ts, "max_eigen_value_left_ex", self.so_lib)
+        return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0]), stats.as_dict()
+
+    # ------------------------------------------------------------------
     def similarity_transform_batched(self, mats: np.ndarray, *, eps: Optional[float] = None,
                                      max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
                                      round_loop=None):

@@ -1014,6 +1014,72 @@ int64_t max_eigen_value_csr_pattern_ex(void* wq, int dtype, uint32_t n, uint64_t
                                        st_stats* stats);
 
 /* ---------------------------------------------------------------------- */
+/* 3i. dense LEFT Perron vector (u A = lambda u), no transposed copy       */
+/* ---------------------------------------------------------------------- */
+
+/* The matrix-free solve of section 3 turned by 90 degrees: s_k[c] =
+ * (sum_r A_0[r][c] x[r]) / x[c], x = v_{k-2} * s_{k-1}, on the row-major
+ * matrix where it lies.  What it returns is the Perron pair of A^T: lambda
+ * and the LEFT vector u of A (the stationary distribution of a row-stochastic
+ * A, up to its scale).  d_mat: device pointer, dim x dim row-major, READ ONLY
+ * - never written and never copied on the device; the only workspace is the
+ * vectors and ceil(dim / RB) * dim elements of partial sums (RB:
+ * st_left_shape).  d_eigen_vec / eigen_vec_host / eigen_val / iter_cnt as
+ * st_solve_device_*.  opt: eps, max_itr, semantics and batch as there;
+ * ST_FLAG_MATRIX_FREE is accepted and implied, ST_FLAG_TIME_KERNELS and
+ * ST_FLAG_TRACE_SUMS work (st_last_round_times, st_last_round_sums: the
+ * COLUMN sums every round evaluated); ST_FLAG_ROUND_LOOP,
+ * ST_FLAG_WRITE_EVERY_ROUND and ST_FLAG_BATCH_ROUNDS are errors ("not
+ * supported"), as are a NULL matrix and dim == 0 - checked before anything is
+ * enqueued, never a fallback.  v and the whole st_state of every round are
+ * bit for bit what st_solve_device_* with ST_FLAG_MATRIX_FREE computes from
+ * the same sums; the sums themselves follow the column order below, so
+ * lambda, v and the counts agree with the solve of a transposed copy to
+ * rounding.  Returns loop ms or negative. */
+int64_t st_solve_device_left_f32(void* wq, const float* d_mat, unsigned int dim,
+                                 float* d_eigen_vec, float* eigen_vec_host,
+                                 float* eigen_val, unsigned int* iter_cnt,
+                                 const st_options* opt, st_stats* stats);
+int64_t st_solve_device_left_f64(void* wq, const double* d_mat, unsigned int dim,
+                                 double* d_eigen_vec, double* eigen_vec_host,
+                                 double* eigen_val, unsigned int* iter_cnt,
+                                 const st_options* opt, st_stats* stats);
+/* The host-pointer twin (dtype: 0 = float32, 1 = float64): checks opt's
+ * flags and semantics, the matrix, dim, the outputs and the queue, in that
+ * order, then copies the dim * dim elements of `mat` in as they are, solves,
+ * copies out.  Returns h2d + loop ms or negative. */
+int64_t max_eigen_value_left_ex(void* wq, int dtype, const void* mat,
+                                void* eigen_val, void* eigen_vec,
+                                unsigned int dim, unsigned int* iter_cnt,
+                                const st_options* opt, st_stats* stats);
+/* The summation order of a column, which is a function of (dtype, n) alone:
+ * the rows are cut into blocks of *rows_per_block consecutive rows (the last
+ * one shorter); within a block one accumulator starts from 0 and takes the
+ * rows in ascending order, one fused multiply-add each (launch 0: the same
+ * fma with 1); *combine says how the block values are added: 0 = serially in
+ * ascending block order starting from block 0's value, 1 = a balanced tree
+ * (this build: always 0).  Neither the grid, the strip a column falls in, the
+ * vector width, the rows in flight nor the kind of load enters.  Either
+ * pointer may be NULL.  Returns 0, or negative for a dtype other than 0 / 1
+ * or n outside [1, 2^31).  No GPU needed. */
+int st_left_shape(int dtype, unsigned int n, uint32_t* rows_per_block,
+                  uint32_t* combine);
+/* ELEMENTS of the step-level scratch of st_colsum_* / st_mfree_left_round_*:
+ * x (n, rounded up to 64) then the partials, ceil(n / rows_per_block) * n.
+ * 0 with an error message for a bad dtype or n.  No GPU needed. */
+uint64_t st_left_scratch(int dtype, unsigned int n);
+/* The launch shape the kernels were built with ("block=256 bytes_per_load=16
+ * rows_in_flight=8 rows_per_block=32,64,128,256 rows_from=1,2048,4096,16384
+ * combine=serial finish_block=64 prep_grid=2048 nt_from_mib=512": a workgroup
+ * owns rows_per_block rows by a strip of block * (16 / sizeof(element))
+ * columns - block columns when n * sizeof(element) is no multiple of 16 -, a
+ * lane 16 bytes of each row with 8 rows' loads issued before the first fma;
+ * rows_per_block by the n it starts from; non-temporal loads from 512 MiB);
+ * tools record it next to their numbers (tools/bench_left.py).  No GPU
+ * needed. */
+const char* st_left_shape_desc(void);
+
+/* ---------------------------------------------------------------------- */
 /* 4. step-level kernels (asynchronous on `stream`, a hipStream_t or NULL) */
 /* ---------------------------------------------------------------------- */
 
@@ -1362,6 +1428,42 @@ int st_narrow_f32(int storage, const float* d_in, void* d_out, uint64_t count,
  * GB/s, against 0.161 / 0.627 ms for st_mfree_round_f32 on the widened
  * matrix.  No GPU needed. */
 const char* st_half_shape_desc(void);
+
+/* The dense left-vector scheme, step by step (section 3i; what
+ * st_solve_device_left_* runs).  d_mat / d_mat0: n x n row-major, read only;
+ * all vectors device [n]; d_scratch: st_left_scratch(dtype, n) elements,
+ * 256-byte aligned, distinct from the four vectors.
+ *   st_colsum_*           d_s[c] = sum_r A[r][c] in st_left_shape's order
+ *     (launch 0: s_0); only the partials' part of d_scratch is used
+ *   st_mfree_left_round_* launch k >= 1, the contract of st_mfree_round_* in
+ *     three launches: k_csr_prep writes x = v_prev * s_prev to the start of
+ *     d_scratch and folds max and the stop test of s_prev through d_state,
+ *     its last workgroup publishing round k-1; k_left_sweep writes the column
+ *     products of every row block behind x; k_left_finish adds them and
+ *     writes s_next[c] = t / x[c] and v_cur[c] = v_prev[c] * (s_prev[c] / m).
+ *     d_v_cur and every field of st_state are bit for bit what
+ *     st_mfree_round_* writes for the transposed matrix and the same
+ *     arguments.  All three are no-ops once d_state->end says an earlier
+ *     round stopped.
+ * 16-byte loads when n * sizeof(element) is a multiple of 16 and d_mat and
+ * d_scratch are 16-byte aligned; otherwise element-wide (same bits).
+ * Nothing outside the n * n elements of the matrix is read. */
+int st_colsum_f32(const float* d_mat, float* d_s, float* d_scratch, unsigned int n,
+                  void* stream);
+int st_colsum_f64(const double* d_mat, double* d_s, double* d_scratch,
+                  unsigned int n, void* stream);
+int st_mfree_left_round_f32(const float* d_mat0, const float* d_s_prev,
+                            float* d_s_next, const float* d_v_prev, float* d_v_cur,
+                            float* d_scratch, unsigned int n, float eps,
+                            unsigned int k, unsigned int max_itr,
+                            unsigned int semantics, st_state* d_state,
+                            void* stream);
+int st_mfree_left_round_f64(const double* d_mat0, const double* d_s_prev,
+                            double* d_s_next, const double* d_v_prev,
+                            double* d_v_cur, double* d_scratch, unsigned int n,
+                            double eps, unsigned int k, unsigned int max_itr,
+                            unsigned int semantics, st_state* d_state,
+                            void* stream);
 
 /* The sparse (CSR) scheme, step by step (what st_solve_csr runs); `csr` is a
  * st_csr_create handle, all vectors device [n] in the handle's dtype.
