@@ -712,16 +712,27 @@ def csr_transpose_shape(L: Optional[ctypes.CDLL] = None) -> dict:
 def left_shape(dtype_code: int, n: int, L: Optional[ctypes.CDLL] = None) -> dict:
     """st_left_shape and st_left_shape_desc for one (dtype, n), no GPU: rows
     (RB of the order contract), combine (0 serial, 1 tree), block, w (columns
-    per lane when the row stride allows 16-byte loads) and strip = block * w."""
+    per lane when the row stride allows 16-byte loads) and strip = block * w;
+    rows_table / rows_from (the table's values and the n each holds from),
+    rows_in_flight, nt_from_mib and nt (whether this n's sweeps load
+    non-temporally: n * n elements reach nt_from_mib MiB, as left::grid
+    decides it)."""
     L = L or load()
     rows, comb = ctypes.c_uint32(), ctypes.c_uint32()
     check(L.st_left_shape(dtype_code, n, ctypes.byref(rows), ctypes.byref(comb)),
           "st_left_shape", L)
     desc = dict(kv.split("=") for kv in L.st_left_shape_desc().decode().split())
     block = int(desc["block"])
-    w = int(desc["bytes_per_load"]) // (8 if dtype_code == DTYPE_F64 else 4)
+    elem = 8 if dtype_code == DTYPE_F64 else 4
+    w = int(desc["bytes_per_load"]) // elem
+    nt_from_mib = int(desc["nt_from_mib"])
     return {"rows": rows.value, "combine": comb.value, "block": block, "w": w,
-            "strip": block * w}
+            "strip": block * w,
+            "rows_table": [int(v) for v in desc["rows_per_block"].split(",")],
+            "rows_from": [int(v) for v in desc["rows_from"].split(",")],
+            "rows_in_flight": int(desc["rows_in_flight"]),
+            "nt_from_mib": nt_from_mib,
+            "nt": n * n >= (nt_from_mib << 20) // elem}
 
 
 def round_sums(L: ctypes.CDLL, q, n: int, dtype):

@@ -1,11 +1,17 @@
 """CPU: the host model of the dense left-vector order (dense_left_order_model)
 and the power of its inputs - every wrong order tried must show in at least
 three columns of every value regime and dtype, or a device test that compares
-bytes with the model would prove nothing.  No GPU needed."""
+bytes with the model would prove nothing.  No GPU needed.
+
+The second half does the same for the large sizes of
+test_gpu_dense_left_large.py (dense_left_large): what the size list holds, and
+that the slabs tell every wrong order and every other value of the
+rows-per-block table apart at every one of those sizes."""
 import numpy as np
 import pytest
 
 import csr_order_model as com
+import dense_left_large as dll
 import dense_left_order_model as dlm
 
 DTYPES = ("float32", "float64")
@@ -127,3 +133,103 @@ def test_regimes_hold_what_they_claim():
         assert (A[:, 1] == 0).all() and 0.05 < (A == 0).mean() < 0.2
         A, _, _ = dlm.regime("B", dt, n)
         assert A.max() / A.min() > 2.0 ** 30
+
+
+# ---------------------------------------------------------------------------
+# the large sizes (test_gpu_dense_left_large.py)
+# ---------------------------------------------------------------------------
+LARGE = [(dt, role) for dt in dll.DTYPES for role in dll.ROLES]   # (nothing loaded to list them)
+
+
+def test_large_sizes_hold_what_the_kernels_branch_on():
+    for dt in DTYPES:
+        S = sorted(dll.sizes(dt).values())
+        assert len(set(S)) == len(dll.ROLES)              # no role repeats another's size
+        F = {n: dll.facts(dt, n) for n in S}
+        table, lanes = F[S[0]]["table"], F[S[0]]["lanes"]
+        assert lanes > 1 and len(table) >= 2 and table == sorted(table)
+        # every value of the table, with 16-byte lanes and element-wide
+        for rb in table:
+            assert {F[n]["w"] for n in S if F[n]["rb"] == rb} == {1, lanes}, (dt, rb)
+        # one below and one on every step
+        for step in F[S[0]]["from"][1:]:
+            assert step - 1 in S and step in S and F[step - 1]["rb"] < F[step]["rb"], (dt, step)
+        # both sides of the non-temporal threshold in both lane widths, adjacent to it
+        n0 = dll.first_nt(dt)
+        edge = dll.nt_edge(dt)
+        assert set(edge) == {(nt, w) for nt in (False, True) for w in (1, lanes)}
+        for (nt, w), n in edge.items():
+            assert n in S and (F[n]["nt"], F[n]["w"]) == (nt, w), (dt, n)
+            assert n0 - lanes <= n < n0 + lanes
+        assert n0 - 1 in S and n0 in S
+        # more than one strip of 16-byte lanes in every class from the second on
+        for rb in table[1:]:
+            assert any(F[n]["rb"] == rb and F[n]["w"] > 1 and F[n]["nstrips"] >= 2 for n in S)
+        # a last block shorter than the rows in flight, with a partial last strip
+        for rb in table[1:]:
+            assert any(F[n]["rb"] == rb and F[n]["w"] > 1 and F[n]["last"] < F[n]["in_flight"]
+                       and n % F[n]["strip"] for n in S), (dt, rb)
+        # the finish's 16-wide loop: more than two trips, and whole trips without a remainder
+        assert any(F[n]["nrb"] > 33 for n in S)
+        assert any(F[n]["nrb"] > 33 and (F[n]["nrb"] - 1) % 16 == 0 for n in S)
+        assert all(8 * n < 2 ** 24 for n in S)            # the exact-input test's claim
+
+
+def test_large_columns_hold_the_boundaries():
+    for dt, role in LARGE:
+        n = dll.sizes(dt)[role]
+        f = dll.facts(dt, n)
+        cols = dll.model_columns(dt, n)
+        w, strip = f["w"], f["strip"]
+        assert len(cols) == dll.COLUMNS == len(set(cols)) and cols == sorted(cols)
+        assert {0, w - 1, w, strip - 1, strip, strip + 1, (f["nstrips"] - 1) * strip, n - w - 1,
+                n - w, n - 1} <= set(cols), (dt, n)
+        assert dll.model_columns(dt, n) == cols
+
+
+def test_large_slabs_hold_what_they_claim():
+    for dt in DTYPES:
+        n = dll.sizes(dt)["below1"]
+        cols = tuple(dll.model_columns(dt, n))
+        tiny = np.finfo(dt).tiny
+        S, s, v = dll.slab("C", dt, n, cols)
+        assert S.shape == (n, len(cols)) and S.dtype == np.dtype(dt)
+        assert (S[:, dll.SUBNORMAL_AT] < tiny).all() and (S[:, dll.SUBNORMAL_AT] > 0).all()
+        prod = S[:, 0].astype(np.longdouble) * (v * s).astype(np.longdouble)
+        assert (prod < tiny).any()                    # subnormal products
+        S, _, _ = dll.slab("D", dt, n, cols)
+        assert (S[:, dll.ZERO_AT] == 0).all() and 0.05 < (S[:, :dll.PINNED] == 0).mean() < 0.2
+        S, _, _ = dll.slab("B", dt, n, cols)
+        assert S.max() / S.min() > 2.0 ** 30
+        S, s, v = dll.slab("A", dt, n, cols)
+        assert S.min() > 0 and S.max() <= 1 and 0.5 <= min(s.min(), v.min())
+        # a function of (name, dtype, n, number of columns, draw): drawn again, the same bytes
+        again = dll.slab("A", dt, n, tuple(reversed(cols)))
+        assert all(a.tobytes() == b.tobytes() for a, b in zip((S, s, v), again))
+        draw = dll.golden()[dt][str(n)]["draw"]["A"]
+        assert S.tobytes() != dll.slab("A", dt, n, cols, draw + 1)[0].tobytes()
+        S, _, _ = dll.slab("B", dt, n, cols)
+        assert (S[n - 1] >= S.max() / 2).all()        # the last row at the top of the range
+
+
+@pytest.mark.parametrize("dt,role", LARGE)
+def test_large_slabs_tell_wrong_orders_and_other_table_values_apart(dt, role):
+    """For every regime, launch 1 and launch 0: each wrong order of dlm.WRONG,
+    and the model run with each OTHER value of the rows-per-block table - what
+    an edit of the table would compute - differs from the model with the
+    library's value in at least MIN_COLUMNS of the slab's 16 columns
+    (dense_left_large.unseen).  One column does not always separate two table
+    values, hence a claim over the set.
+
+    The model's own bytes on the first columns are pinned in
+    tests/golden/dense_left_large_order.json: an edit of the table fails here,
+    without a GPU, at exactly the sizes whose order it changes."""
+    assert dll.MIN_COLUMNS == MIN_COLUMNS and len(dlm.WRONG) == 7
+    n = dll.sizes(dt)[role]
+    f = dll.facts(dt, n)
+    assert (f["rb"], f["combine"]) == dlm.shape(dt, n) and len(set(f["table"])) == 4
+    value = {name: {} for name in dlm.REGIMES}
+    unseen = {name: dll.unseen(name, dt, n, None, value[name]) for name in dlm.REGIMES}
+    assert dll.digest(dt, n, value) == dll.golden()[dt][str(n)]["order"], \
+        (dt, n, f["rb"], "the expected bytes of this size changed")
+    assert not any(unseen.values()), (dt, n, unseen)
