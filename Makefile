@@ -12,7 +12,7 @@ SRC      := eigen_value_amd/csrc/st_kernels.hip eigen_value_amd/csrc/st_solve.hi
             eigen_value_amd/csrc/st_csr_batch.hip eigen_value_amd/csrc/st_csr_transpose.hip \
             eigen_value_amd/csrc/st_csr_terms.hip eigen_value_amd/csrc/st_csr_multi.hip \
             eigen_value_amd/csrc/st_csr_product.hip eigen_value_amd/csrc/st_csr_pattern.hip \
-            eigen_value_amd/csrc/st_left.hip
+            eigen_value_amd/csrc/st_left.hip eigen_value_amd/csrc/st_pair.hip
 OBJ     := $(patsubst eigen_value_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB      := eigen_value_amd/lib/libsimilarity_transform.so
 # the tuning build (tools and the knob tests only): the same objects, with
@@ -28,7 +28,8 @@ HDRS     := include/similarity_transform.h include/st_tuning.h eigen_value_amd/c
             eigen_value_amd/csrc/st_csr_plan.h eigen_value_amd/csrc/st_csr_transpose.h \
             eigen_value_amd/csrc/st_csr_terms.h eigen_value_amd/csrc/st_csr_multi.h \
             eigen_value_amd/csrc/st_csr_product.h eigen_value_amd/csrc/st_csr_pattern.h \
-            eigen_value_amd/csrc/st_left.h eigen_value_amd/csrc/st_left_host.h
+            eigen_value_amd/csrc/st_left.h eigen_value_amd/csrc/st_left_host.h \
+            eigen_value_amd/csrc/st_pair.h eigen_value_amd/csrc/st_pair_host.h
 
 all: $(LIB) $(LIB_TUNING) oracle
 
@@ -122,9 +123,20 @@ left_sanitize: tests/cpp/left_sanitize.cpp eigen_value_amd/csrc/st_left_host.h
 	  -o build/left_sanitize
 	./build/left_sanitize
 
+# the host arithmetic of the dense pair solve (st_pair_host.h: the strip, the
+# scratch layout and the launch grid, every tile walked as the kernel's lanes
+# walk it) under the host sanitizers, as left_sanitize
+pair_sanitize: tests/cpp/pair_sanitize.cpp eigen_value_amd/csrc/st_pair_host.h \
+               eigen_value_amd/csrc/st_left_host.h
+	@mkdir -p build
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	  -fno-omit-frame-pointer -Ieigen_value_amd/csrc tests/cpp/pair_sanitize.cpp \
+	  -o build/pair_sanitize
+	./build/pair_sanitize
+
 clean:
 	rm -rf build eigen_value_amd/lib
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean probe csr_terms_sanitize csr_multi_sanitize csr_product_sanitize \
-        csr_pattern_sanitize left_sanitize
+        csr_pattern_sanitize left_sanitize pair_sanitize

@@ -323,6 +323,23 @@ def _declare(L: ctypes.CDLL) -> None:
     L.st_left_scratch.restype = u64
     L.st_left_shape_desc.argtypes = []
     L.st_left_shape_desc.restype = ctypes.c_char_p
+    # dense Perron pair (both vectors from one pass over the matrix per round)
+    for sfx, T in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        getattr(L, f"st_solve_device_pair_{sfx}").argtypes = [P, P, u32, P, P, P, P, P, P, P]
+        getattr(L, f"st_solve_device_pair_{sfx}").restype = i64
+        getattr(L, f"st_pair_sum_{sfx}").argtypes = [P, P, P, P, u32, P]
+        getattr(L, f"st_pair_sum_{sfx}").restype = i32
+        getattr(L, f"st_mfree_pair_round_{sfx}").argtypes = [P] * 10 + [u32, T, u32, u32, u32,
+                                                                      P, P]
+        getattr(L, f"st_mfree_pair_round_{sfx}").restype = i32
+    L.max_eigen_value_pair_ex.argtypes = [P, i32, P, P, P, u32, P, P, P, P]
+    L.max_eigen_value_pair_ex.restype = i64
+    L.st_pair_shape.argtypes = [i32, u32, P, P, P, P]
+    L.st_pair_shape.restype = i32
+    L.st_pair_scratch.argtypes = [i32, u32]
+    L.st_pair_scratch.restype = u64
+    L.st_pair_shape_desc.argtypes = []
+    L.st_pair_shape_desc.restype = ctypes.c_char_p
     # sparse (CSR) solve
     L.st_csr_class_limits.argtypes = [i32, P, P, i32]
     L.st_csr_class_limits.restype = i32
@@ -731,6 +748,29 @@ def left_shape(dtype_code: int, n: int, L: Optional[ctypes.CDLL] = None) -> dict
             "rows_table": [int(v) for v in desc["rows_per_block"].split(",")],
             "rows_from": [int(v) for v in desc["rows_from"].split(",")],
             "rows_in_flight": int(desc["rows_in_flight"]),
+            "nt_from_mib": nt_from_mib,
+            "nt": n * n >= (nt_from_mib << 20) // elem}
+
+
+def pair_shape(dtype_code: int, n: int, L: Optional[ctypes.CDLL] = None) -> dict:
+    """st_pair_shape and st_pair_shape_desc for one (dtype, n), no GPU: rows
+    (RB, st_left_shape's), strip (S: the columns of a workgroup, part of a
+    row's order), combine_left / combine_right (0 serial), block, w (columns
+    per lane = 16 bytes of elements, whatever the kind of load), nstrips,
+    rows_in_flight, lds_rows, nt_from_mib and nt."""
+    L = L or load()
+    rows, strip, cl, cr = (ctypes.c_uint32() for _ in range(4))
+    check(L.st_pair_shape(dtype_code, n, ctypes.byref(rows), ctypes.byref(strip),
+                          ctypes.byref(cl), ctypes.byref(cr)), "st_pair_shape", L)
+    desc = dict(kv.split("=") for kv in L.st_pair_shape_desc().decode().split())
+    elem = 8 if dtype_code == DTYPE_F64 else 4
+    nt_from_mib = int(desc["nt_from_mib"])
+    return {"rows": rows.value, "strip": strip.value, "combine_left": cl.value,
+            "combine_right": cr.value, "block": int(desc["block"]),
+            "w": int(desc["bytes_per_load"]) // elem,
+            "nstrips": -(-n // strip.value),
+            "rows_in_flight": int(desc["rows_in_flight"]),
+            "lds_rows": int(desc["lds_rows"]),
             "nt_from_mib": nt_from_mib,
             "nt": n * n >= (nt_from_mib << 20) // elem}
 

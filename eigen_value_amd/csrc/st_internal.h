@@ -155,6 +155,28 @@ int launch_left_round(const T* a, const T* s_prev, T* s_next, const T* v_prev,
                       T* v_cur, T* x, T* part, uint32_t n, T eps, uint32_t k,
                       uint32_t max_itr, uint32_t semantics, st_state* st,
                       hipStream_t stream);
+// the dense Perron pair round (st_pair.hip): both vectors of an n x n matrix
+// that is only read, from one pass over it per launch.  Index 0 of every pair
+// is the right side, index 1 the left one; scratch holds
+// pair_scratch_elems(dtype, n) elements ([x_R | x_L | colpart | rowpart]).
+// d_count (may be null): where the launch's last kernel leaves the number of
+// sides whose state is done
+template <typename T>
+struct PairVectors
+{
+  const T* s_prev[2];
+  T* s_next[2];
+  const T* v_prev[2];
+  T* v_cur[2];
+};
+size_t pair_scratch_elems(int dtype, uint32_t n);
+template <typename T>
+int launch_pair_sum(const T* a, T* s_right, T* s_left, T* scratch, uint32_t n,
+                    hipStream_t stream);
+template <typename T>
+int launch_pair_round(const T* a, const PairVectors<T>& v, T* scratch, uint32_t n, T eps,
+                      uint32_t k, uint32_t max_itr, uint32_t semantics, st_state* st,
+                      uint32_t* d_count, hipStream_t stream);
 // the sparse (CSR) solve (st_csr.hip): a validated matrix with its plan.
 // The three arrays stay the caller's; order is the handle's own.
 struct CsrHandle

@@ -26,7 +26,8 @@
 // covering the whole batch (k_round_batched, solve_batched_rounds).  The
 // batched forms that enqueue rounds (solve_batched_rounds, the batched and
 // the multi-column CSR solves) share counted_rounds; all five batched forms
-// share report_entries.  The host-pointer twins lay their workspace out with
+// share report_entries; the dense pair solve (solve_pair_t: two sides of one
+// matrix) uses both.  The host-pointer twins lay their workspace out with
 // CsrSlots / VecSlots and end in finish_twin.
 // The reference blocks on a host_accessor every round
 // (similarity_transform.cpp:45-50).  Here rounds are enqueued in batches;
@@ -49,6 +50,7 @@
 #include "st_csr_host.h"
 #include "st_internal.h"
 #include "st_left_host.h"
+#include "st_pair_host.h"
 
 namespace st {
 
@@ -1761,6 +1763,161 @@ solve_csr_multi(Context* c, const CsrHandle* h, const CsrMultiHandle* t, void* d
     static_cast<float*>(eigen_vals), iter_cnts, converged, o, stats);
 }
 
+// The Perron pair of a device-resident dense matrix (A v = lambda v and
+// u A = lambda u): solve_csr_multi_t's host loop - one memset of the two
+// states and the finished counter, one fill of both v, launch 0, then
+// opt->batch rounds per look at the mirrored counter - with st_pair.hip's five
+// launches per round, whose sweep reads the matrix once for both sides.  Each
+// side keeps its own state and stops in its own round; its eigenvector lies in
+// the ping-pong buffer its end's parity names.  The matrix is only read and
+// never copied.  Workspace: [s_R0 | s_R1 | s_L0 | s_L1 | v_R0 | v_L0 | v_R1 |
+// v_L1] in the vector buffer, the round's scratch in the partials' buffer.
+// Everything is checked before anything is enqueued.
+int
+pair_check_flags(const st_options* opt)
+{
+  const uint32_t flags = opt ? opt->flags : 0u;
+  constexpr uint32_t kNo = ST_FLAG_TIME_KERNELS | ST_FLAG_TRACE_SUMS |
+                           ST_FLAG_ROUND_LOOP | ST_FLAG_WRITE_EVERY_ROUND |
+                           ST_FLAG_BATCH_ROUNDS;
+  ST_REQUIRE((flags & kNo) == 0,
+             "dense pair solve: ST_FLAG_TIME_KERNELS, ST_FLAG_TRACE_SUMS, "
+             "ST_FLAG_ROUND_LOOP, ST_FLAG_WRITE_EVERY_ROUND and "
+             "ST_FLAG_BATCH_ROUNDS are not supported (flags = %u): the matrix is "
+             "read only and every round is the same five launches for both sides",
+             flags);
+  return 0;
+}
+
+template <typename T>
+int64_t
+solve_pair_t(Context* c, const T* d_mat, uint32_t n, T* d_v_out, T* v_host, T* eigen_vals,
+             uint32_t* iter_cnts, uint32_t* converged, const Resolved& o, st_stats* stats)
+{
+  {
+    left::Grid g;
+    uint64_t want = 0;
+    ST_REQUIRE(pair::grid(n, left_rows(sizeof(T) == 8, n), sizeof(T), &g, &want),
+               "dense pair: dim = %u needs %llu workgroups per launch, above %llu", n,
+               (unsigned long long)want, (unsigned long long)left::kGridMax);
+  }
+  const size_t v_bytes = sizeof(T) * (size_t)n;
+  if (ensure_device(c) || ensure_vectors(c, v_bytes) || ensure_bstate(c, 2) ||
+      ensure_bsum(c, 256) ||
+      c->part.ensure(c->stream, sizeof(T) * pair_scratch_elems(sizeof(T) == 8, n)))
+    return -1;
+  T* sb[2][2] = { { c->vec_slot<T>(0), c->vec_slot<T>(1) },   // [side][parity]
+                  { c->vec_slot<T>(2), c->vec_slot<T>(3) } };
+  T* vb[2][2] = { { c->vec_slot<T>(4), c->vec_slot<T>(6) },   // both v_0 adjacent
+                  { c->vec_slot<T>(5), c->vec_slot<T>(7) } };
+  T* scratch = static_cast<T*>(c->part.p);
+  hipStream_t s = c->stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemsetAsync(c->bstate.p, 0, sizeof(st_state) * 2, s));
+  ST_CHECK(hipMemsetAsync(c->d_bcount, 0, sizeof(uint32_t), s));
+  if (launch_fill<T>(vb[0][0], (uint64_t)(c->vec_bytes / sizeof(T)) + n, (T)1, s))
+    return -1;
+  if (launch_pair_sum<T>(d_mat, sb[pair::kRight][0], sb[pair::kLeft][0], scratch, n, s))
+    return -1;
+  const int64_t enqueued = counted_rounds(
+    c, o.batch ? o.batch : kDefaultBatch, o.max_itr, 2,
+    [&](uint32_t k) { // launch k+1 evaluates round k
+      const uint32_t a = k & 1, b = (k + 1) & 1;
+      const PairVectors<T> v = { { sb[0][a], sb[1][a] },
+                                 { sb[0][b], sb[1][b] },
+                                 { vb[0][a], vb[1][a] },
+                                 { vb[0][b], vb[1][b] } };
+      return launch_pair_round<T>(d_mat, v, scratch, n, (T)o.eps, k + 1, o.max_itr,
+                                  o.semantics, c->d_bstate(), c->d_bcount, s);
+    });
+  if (enqueued < 0)
+    return -1;
+  ST_CHECK(hipStreamSynchronize(s));
+  st_state res[2];
+  ST_CHECK(hipMemcpy(res, c->bstate.p, sizeof(res), hipMemcpyDeviceToHost));
+  const double loop_ms = ms_since(t0);
+  st_stats local{};
+  const int64_t rc =
+    report_entries<T>(res, 2, "side", eigen_vals, iter_cnts, converged, (T*)nullptr,
+                      (const T*)nullptr, 0, loop_ms, (uint32_t)enqueued, &local);
+  if (rc < 0)
+    return -1;
+  const auto t1 = std::chrono::steady_clock::now();
+  for (uint32_t side = 0; side < 2; side++) { // launch `end` wrote v into buffer end & 1
+    const T* fin = vb[side][res[side].end & 1u];
+    if (d_v_out)
+      ST_CHECK(hipMemcpyAsync(d_v_out + (size_t)side * n, fin, v_bytes,
+                              hipMemcpyDeviceToDevice, s));
+    if (v_host)
+      ST_CHECK(hipMemcpyAsync(v_host + (size_t)side * n, fin, v_bytes,
+                              hipMemcpyDeviceToHost, s));
+  }
+  ST_CHECK(hipStreamSynchronize(s));
+  local.d2h_ms = ms_since(t1);
+  if (stats)
+    *stats = local;
+  return rc;
+}
+
+template <typename T>
+int64_t
+solve_device_pair(Context* c, const T* d_mat, uint32_t n, T* d_v_out, T* v_host,
+                  T* eigen_vals, uint32_t* iter_cnts, uint32_t* converged,
+                  const st_options* opt, st_stats* stats)
+{
+  if (pair_check_flags(opt))
+    return -1;
+  Resolved o;
+  if (resolve<T>(opt, &o))
+    return -1;
+  ST_REQUIRE(d_mat, "dense pair solve: null matrix");
+  ST_REQUIRE(n > 0, "dense pair solve: dim must be > 0");
+  ST_REQUIRE(((uintptr_t)d_mat & (sizeof(T) - 1)) == 0,
+             "dense pair solve: matrix not aligned to its element size");
+  ST_REQUIRE(eigen_vals && iter_cnts, "null output pointer");
+  ST_REQUIRE(d_v_out || v_host, "need a device or host eigenvector output");
+  ST_REQUIRE(c, "null queue");
+  return solve_pair_t<T>(c, d_mat, n, d_v_out, v_host, eigen_vals, iter_cnts, converged, o,
+                         stats);
+}
+
+// the host twin: max_eigen_value_left_ex's check order and staging (one
+// slot, copied in once and only read; no transposed copy)
+template <typename T>
+int64_t
+solve_host_pair(Context* c, const T* mat, uint32_t n, T* eigen_vals, T* eigen_vecs,
+                uint32_t* iter_cnts, uint32_t* converged, const st_options* opt,
+                st_stats* stats)
+{
+  if (pair_check_flags(opt))
+    return -1;
+  {
+    Resolved o;
+    if (resolve<T>(opt, &o))
+      return -1;
+  }
+  ST_REQUIRE(mat, "max_eigen_value_pair_ex: null matrix");
+  ST_REQUIRE(n > 0, "max_eigen_value_pair_ex: dim must be > 0");
+  ST_REQUIRE(eigen_vals && eigen_vecs && iter_cnts, "null output pointer");
+  ST_REQUIRE(c, "null queue");
+  if (ensure_device(c))
+    return -1;
+  ST_REQUIRE(n <= left::kNMax && left::stage_fits(n, sizeof(T)),
+             "max_eigen_value_pair_ex: dim = %u is too large", n);
+  if (c->mat.ensure(c->stream, (size_t)left::stage_bytes(n, sizeof(T))))
+    return -1;
+  const auto t0 = std::chrono::steady_clock::now();
+  ST_CHECK(hipMemcpyAsync(c->mat.p, mat, sizeof(T) * (size_t)n * n, hipMemcpyHostToDevice,
+                          c->stream));
+  ST_CHECK(hipStreamSynchronize(c->stream));
+  const double h2d = ms_since(t0);
+  st_stats local{};
+  if (solve_device_pair<T>(c, static_cast<const T*>(c->mat.p), n, nullptr, eigen_vecs,
+                           eigen_vals, iter_cnts, converged, opt, &local) < 0)
+    return -1;
+  return finish_twin(local, h2d, stats);
+}
+
 // The host-pointer twin: everything validated on the host first (dtype,
 // flags, the matrix, C and K, then column after column the vectors and the
 // rows of M_c), the terms packed on the host (csr::pack_columns) and copied
@@ -2609,6 +2766,41 @@ max_eigen_value_left_ex(void* wq, int dtype, const void* mat, void* eigen_val,
                                        (double*)eigen_val, (double*)eigen_vec, iter_cnt,
                                        opt, stats);
   st::set_error("max_eigen_value_left_ex: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
+  return -1;
+}
+
+#define ST_PAIR_SOLVE(T, SFX)                                                           \
+  int64_t st_solve_device_pair_##SFX(void* wq, const T* d_mat, unsigned int dim,        \
+                                     T* d_eigen_vecs, T* eigen_vecs_host, T* eigen_vals, \
+                                     unsigned int* iter_cnts, unsigned int* converged,   \
+                                     const st_options* opt, st_stats* stats)             \
+  {                                                                                     \
+    st::clear_error();                                                                  \
+    st::DeviceGuard guard;                                                              \
+    return st::solve_device_pair<T>(st::as_ctx(wq), d_mat, dim, d_eigen_vecs,           \
+                                    eigen_vecs_host, eigen_vals, iter_cnts, converged,  \
+                                    opt, stats);                                        \
+  }
+ST_PAIR_SOLVE(float, f32)
+ST_PAIR_SOLVE(double, f64)
+#undef ST_PAIR_SOLVE
+
+int64_t
+max_eigen_value_pair_ex(void* wq, int dtype, const void* mat, void* eigen_vals,
+                        void* eigen_vecs, unsigned int dim, unsigned int* iter_cnts,
+                        unsigned int* converged, const st_options* opt, st_stats* stats)
+{
+  st::clear_error();
+  st::DeviceGuard guard;
+  if (dtype == 0)
+    return st::solve_host_pair<float>(st::as_ctx(wq), (const float*)mat, dim,
+                                      (float*)eigen_vals, (float*)eigen_vecs, iter_cnts,
+                                      converged, opt, stats);
+  if (dtype == 1)
+    return st::solve_host_pair<double>(st::as_ctx(wq), (const double*)mat, dim,
+                                       (double*)eigen_vals, (double*)eigen_vecs, iter_cnts,
+                                       converged, opt, stats);
+  st::set_error("max_eigen_value_pair_ex: dtype must be 0 (f32) or 1 (f64), got %d", dtype);
   return -1;
 }
 

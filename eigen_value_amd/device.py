@@ -238,6 +238,58 @@ def mfree_left_round(mat0, s_prev, s_next, v_prev, v_cur, scratch, state, *,
         eps, k, max_itr, semantics, _ptr(state), _stream(mat0.device)), "mfree_left_round")
 
 
+def pair_scratch(n: int, dtype, device="cuda"):
+    """The scratch of ``pair_sum`` / ``mfree_pair_round`` for an n x n matrix
+    (``st_pair_scratch`` elements: x_R, x_L, the column partials, the row
+    partials)."""
+    torch = _torch()
+    count = int(_lib.load().st_pair_scratch(_dtype_code(dtype), n))
+    if count == 0:
+        raise _lib.EigenValueError(f"st_pair_scratch: {_lib.last_error()}")
+    return torch.empty(count, dtype=dtype, device=device)
+
+
+def pair_sum(mat, out_right=None, out_left=None, scratch=None):
+    """(s_right, s_left): the row sums and the column sums of the square
+    ``mat`` from one pass over it (``st_pair_sum_*``: launch 0 of the pair
+    solve), in the orders ``st_pair_shape`` publishes."""
+    _check_cuda(mat, out_right, out_left, scratch)
+    assert mat.is_contiguous() and mat.dim() == 2 and mat.shape[0] == mat.shape[1]
+    n = mat.shape[0]
+    out_right = mat.new_empty(n) if out_right is None else out_right
+    out_left = mat.new_empty(n) if out_left is None else out_left
+    assert min(out_right.numel(), out_left.numel()) >= n
+    if scratch is None:
+        scratch = pair_scratch(n, mat.dtype, mat.device)
+    assert scratch.dtype == mat.dtype
+    assert scratch.numel() >= int(_lib.load().st_pair_scratch(_dtype_code(mat.dtype), n))
+    _lib.check(getattr(_lib.load(), f"st_pair_sum_{_sfx(mat)}")(
+        _ptr(mat), _ptr(out_right), _ptr(out_left), _ptr(scratch), n, _stream(mat.device)),
+        "pair_sum")
+    return out_right, out_left
+
+
+def mfree_pair_round(mat0, right, left, scratch, states, *, eps: float = 1e-3, k: int = 1,
+                     max_itr: int = _lib.ST_MAX_ITR,
+                     semantics: int = _lib.ST_SEM_SYCL) -> None:
+    """Launch k >= 1 of the pair solve (``st_mfree_pair_round_*``).  ``right``
+    and ``left`` are ``(s_prev, s_next, v_prev, v_cur)`` of their side,
+    ``states`` two adjacent ``st_state`` (128 bytes: the right side's, then the
+    left side's), ``scratch`` is ``pair_scratch``.  ``mat0`` is only read, once
+    for both sides; a side whose state has ended gets no write."""
+    _check_cuda(mat0, *right, *left, scratch, states)
+    assert mat0.is_contiguous() and mat0.dim() == 2 and mat0.shape[0] == mat0.shape[1]
+    n = mat0.shape[0]
+    assert len(right) == 4 and len(left) == 4
+    assert min(t.numel() for t in (*right, *left)) >= n
+    assert scratch.dtype == mat0.dtype
+    assert scratch.numel() >= int(_lib.load().st_pair_scratch(_dtype_code(mat0.dtype), n))
+    assert states.numel() * states.element_size() >= 128
+    _lib.check(getattr(_lib.load(), f"st_mfree_pair_round_{_sfx(mat0)}")(
+        _ptr(mat0), *(_ptr(t) for t in right), *(_ptr(t) for t in left), _ptr(scratch), n,
+        eps, k, max_itr, semantics, _ptr(states), _stream(mat0.device)), "mfree_pair_round")
+
+
 def _storage(t) -> int:
     """The storage code of a float16 / bfloat16 tensor (ST_STORE_*)."""
     torch = _torch()
@@ -1490,6 +1542,50 @@ class DeviceSolver:
             ctypes.byref(opt), ctypes.byref(stats))
         _lib.check(rc, entry)
         return float(ev.value), v, int(it.value), stats.as_dict()
+
+    def solve_pair(self, mat, *, eps: Optional[float] = None, max_itr: int = 0,
+                   semantics: int = _lib.ST_SEM_SYCL, batch: int = 0):
+        """Both Perron vectors of a dense matrix, ``A v = λ v`` and
+        ``u A = λ u``, from one pass over it per round
+        (``st_solve_device_pair_*``).  Returns (λ: [2] list of float, vecs:
+        [2, n] tensor, iterations: [2] list of int, stats: dict); index 0 is
+        the right side (``vecs[0] = v``), index 1 the left one (``vecs[1] =
+        u``, bit for bit ``solve(mat, left=True)``'s).  The two sides are
+        independent iterations and stop in their own rounds;
+        ``stats["converged_sides"]`` says which did before ``max_itr``.
+
+        ``mat`` (a float32 / float64 tensor or any DLPack producer, square, on
+        this device) is only read and never cloned; a non-contiguous ``mat`` is
+        solved as its contiguous copy; 16-bit tensors raise ``TypeError``
+        (``solve_half`` has no pair form)."""
+        torch = _torch()
+        if not isinstance(mat, torch.Tensor) and hasattr(mat, "__dlpack__"):
+            mat = torch.from_dlpack(mat)   # any DLPack producer, zero copy
+        if mat.dtype in (torch.float16, torch.bfloat16):
+            raise TypeError("solve_pair needs a float32 / float64 matrix: the 16-bit "
+                            f"solve (solve_half) has no pair form, got {mat.dtype}")
+        _check_cuda(mat)
+        if mat.device.index != (self.device.index if self.device.index is not None
+                                else torch.cuda.current_device()):
+            raise ValueError(f"matrix on {mat.device}, solver context on {self.device}")
+        n = mat.shape[0]
+        assert mat.dim() == 2 and mat.shape == (n, n), "must be square"
+        work = mat.contiguous()
+        vecs = torch.empty((2, n), dtype=mat.dtype, device=mat.device)
+        ev = ((ctypes.c_double if mat.dtype == torch.float64 else ctypes.c_float) * 2)()
+        it = (ctypes.c_uint32 * 2)()
+        conv = (ctypes.c_uint32 * 2)()
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, _lib.ST_FLAG_MATRIX_FREE)
+        stats = _lib.st_stats()
+        _lib.check(self.L.st_set_stream(self.q, _stream(mat.device)), "st_set_stream")
+        rc = getattr(self.L, f"st_solve_device_pair_{_sfx(mat)}")(
+            self.q, _ptr(work), n, _ptr(vecs), None, ev, it, conv, ctypes.byref(opt),
+            ctypes.byref(stats))
+        _lib.check(rc, "st_solve_device_pair")
+        out = stats.as_dict()
+        out["converged_sides"] = [int(conv[0]), int(conv[1])]
+        return [float(ev[0]), float(ev[1])], vecs, [int(it[0]), int(it[1])], out
 
     def solve_half(self, mat, *, eps: Optional[float] = None, max_itr: int = 0,
                    semantics: int = _lib.ST_SEM_SYCL, batch: int = 0,

@@ -150,6 +150,40 @@ class EigenValue:
         return eigen_val[0], eigen_vec, int(ts), int(iter_cnt[0]), stats.as_dict()
 
     # ------------------------------------------------------------------
+    def similarity_transform_pair(self, mat: np.ndarray, *, eps: Optional[float] = None,
+                                  max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
+                                  batch: int = 0):
+        """Both Perron vectors of a dense matrix, ``A v = λ v`` and
+        ``u A = λ u`` (``max_eigen_value_pair_ex``): two independent
+        iterations that share one pass over the matrix per round, on the matrix
+        as it is stored - one copy in, no transposed copy.  Index 0 is the
+        right side, index 1 the left one; each side stops in its own round.
+
+        Returns ``(λ [2], vecs [2, n], ts_ms, iterations [2])`` in the dtype
+        of ``mat`` (float32 or float64); ``last_pair_stats`` holds the call's
+        stats and ``converged`` by side."""
+        m, n = mat.shape
+        assert m == n, "must be square matrix of floating points !"
+        mat = np.ascontiguousarray(mat)
+        if mat.dtype not in (np.float32, np.float64):
+            raise TypeError("float32 or float64 matrix required")
+        opt = _lib.st_options(-1.0 if eps is None else float(eps), max_itr, semantics,
+                              batch, _lib.ST_FLAG_MATRIX_FREE)
+        stats = _lib.st_stats()
+        eigen_vals = np.empty(2, dtype=mat.dtype)
+        eigen_vecs = np.empty((2, n), dtype=mat.dtype)
+        iter_cnts = np.zeros(2, dtype=np.uint32)
+        converged = np.zeros(2, dtype=np.uint32)
+        dtype = _lib.DTYPE_F32 if mat.dtype == np.float32 else _lib.DTYPE_F64
+        ts = self.so_lib.max_eigen_value_pair_ex(
+            self.sycl_q, dtype, mat.ctypes.data, eigen_vals.ctypes.data,
+            eigen_vecs.ctypes.data, n, iter_cnts.ctypes.data, converged.ctypes.data,
+            ctypes.byref(opt), ctypes.byref(stats))
+        _lib.check(ts, "max_eigen_value_pair_ex", self.so_lib)
+        self.last_pair_stats = dict(stats.as_dict(), converged_sides=converged.tolist())
+        return eigen_vals, eigen_vecs, int(ts), iter_cnts.astype(np.int64)
+
+    # ------------------------------------------------------------------
     def similarity_transform_batched(self, mats: np.ndarray, *, eps: Optional[float] = None,
                                      max_itr: int = 0, semantics: int = _lib.ST_SEM_SYCL,
                                      round_loop=None):

@@ -12,7 +12,10 @@
  *      wrapper binds (wrapper/python/similarity_transform.py:33-37,63-69).
  *   2. Additions at the same level (fp64 twin, queue teardown, last error,
  *      an extended call with options and statistics).
- *   3. Device-resident solve (input already in HBM; bench and torch users).
+ *   3. Device-resident solve (input already in HBM; bench and torch users);
+ *      3a-3j: batched (3a), multi-GPU (3b), sparse CSR (3c-3h), dense
+ *      left-vector (3i) and dense pair (3j: both Perron vectors from one
+ *      pass over the matrix per round) solves.
  *   4. Step-level kernels on a caller stream: what the row-block sharded
  *      driver (eigen_value_amd/sharded.py) and the kernel unit tests call.
  *
@@ -1080,6 +1083,98 @@ uint64_t st_left_scratch(int dtype, unsigned int n);
 const char* st_left_shape_desc(void);
 
 /* ---------------------------------------------------------------------- */
+/* 3j. dense Perron PAIR: the right and the left vector from one pass over */
+/*     the matrix per round                                                */
+/* ---------------------------------------------------------------------- */
+
+/* side index of every [2] argument below */
+#define ST_PAIR_RIGHT 0 /* A v = lambda v: what st_solve_device_* returns      */
+#define ST_PAIR_LEFT 1  /* u A = lambda u: what st_solve_device_left_* returns */
+
+/* Two independent iterations on one dense matrix - the matrix-free right
+ * iteration s_R = (A x_R) / x_R of section 3 and the left iteration s_L =
+ * (x_L^T A) / x_L of section 3i - each with its own state, vectors and stop
+ * round; they share only the loads of the matrix, which every round reads
+ * once.  d_mat: device pointer, dim x dim row-major, READ ONLY - never written
+ * and never copied on the device; the workspace is the vectors and
+ * st_pair_scratch elements.  d_eigen_vecs (device) / eigen_vecs_host: [2][dim],
+ * either may be NULL but not both; eigen_vals [2], iter_cnts [2], converged
+ * [2] (may be NULL) by side, with st_solve_csr_multi's conventions:
+ * stats->rounds is the larger count, stats->converged is 1 only if both sides
+ * converged, stats->fused_launches is the rounds enqueued.  opt: eps, max_itr,
+ * semantics and batch (rounds per look at the count of finished sides, 0 = 8);
+ * reaching max_itr ends each side on its own.  ST_FLAG_MATRIX_FREE is accepted
+ * and implied; ST_FLAG_TIME_KERNELS, ST_FLAG_TRACE_SUMS, ST_FLAG_ROUND_LOOP,
+ * ST_FLAG_WRITE_EVERY_ROUND and ST_FLAG_BATCH_ROUNDS are errors ("not
+ * supported"), as are a NULL matrix and dim == 0 - checked before anything is
+ * enqueued, never a fallback.
+ *   The left side's sums follow st_left_shape's order: lambda, vector, count
+ * and state of side 1 are bit for bit those of st_solve_device_left_* on the
+ * same matrix.  The right side's sums follow st_pair_shape's order below, not
+ * k_mfree's: its v and state are bit for bit what st_mfree_round_* computes
+ * from the same sums, and lambda, v and the count agree with
+ * st_solve_device_* (ST_FLAG_MATRIX_FREE) to rounding.  Whether one pair solve
+ * is faster than the two solves it replaces is a measured property of the
+ * build and the size: README.md and DESIGN.md carry the numbers
+ * (tools/bench_pair.py).  Returns loop ms or negative. */
+int64_t st_solve_device_pair_f32(void* wq, const float* d_mat, unsigned int dim,
+                                 float* d_eigen_vecs, float* eigen_vecs_host,
+                                 float* eigen_vals, unsigned int* iter_cnts,
+                                 unsigned int* converged, const st_options* opt,
+                                 st_stats* stats);
+int64_t st_solve_device_pair_f64(void* wq, const double* d_mat, unsigned int dim,
+                                 double* d_eigen_vecs, double* eigen_vecs_host,
+                                 double* eigen_vals, unsigned int* iter_cnts,
+                                 unsigned int* converged, const st_options* opt,
+                                 st_stats* stats);
+/* The host-pointer twin (dtype: 0 = float32, 1 = float64): checks opt's
+ * flags and semantics, the matrix, dim, the outputs and the queue, in that
+ * order, then copies the dim * dim elements of `mat` in as they are (one copy,
+ * no transposed copy), solves, copies out.  eigen_vecs: host [2][dim].
+ * Returns h2d + loop ms or negative. */
+int64_t max_eigen_value_pair_ex(void* wq, int dtype, const void* mat,
+                                void* eigen_vals, void* eigen_vecs,
+                                unsigned int dim, unsigned int* iter_cnts,
+                                unsigned int* converged, const st_options* opt,
+                                st_stats* stats);
+/* The summation orders, functions of (dtype, n) alone.  A COLUMN's sum (left
+ * side) is st_left_shape's: blocks of *rows_per_block rows, *combine_left as
+ * its combine.  A ROW's sum (right side): the row is cut into strips of
+ * *strip_cols columns (1024 for float32, 512 for float64, the last one
+ * shorter); in a strip, lane l of 256 takes the 16 / sizeof(element) adjacent
+ * columns from strip * strip_cols + l * (16 / sizeof(element)) in ascending
+ * order, one fused multiply-add each from 0 (launch 0: the same fma with 1;
+ * columns past n left out); the 64 lanes of each of the four waves go through
+ * the balanced tree of every other kernel here (pairs, quads, rows of 16,
+ * (R3 + R2) + (R1 + R0)), the four wave sums are added serially in wave
+ * order, and *combine_right says how the strip values are added: 0 = serially
+ * in ascending strip order starting from strip 0's value (this build: always
+ * 0).  Neither the grid, rows_per_block, the rows in flight nor the kind of
+ * load enters a row's order.  For nonnegative data a row's sum lies within
+ * 16 / sizeof(element) + 6 + 3 + (strips - 1) + 1 ulps of the exact one.  Any
+ * pointer may be NULL.  Returns 0, or negative for a dtype other than 0 / 1
+ * or n outside [1, 2^31).  No GPU needed. */
+int st_pair_shape(int dtype, unsigned int n, uint32_t* rows_per_block,
+                  uint32_t* strip_cols, uint32_t* combine_left,
+                  uint32_t* combine_right);
+/* ELEMENTS of the step-level scratch of st_pair_sum_* / st_mfree_pair_round_*:
+ * [x_R | x_L | column partials | row partials] = 2 * (n rounded up to 64) +
+ * (ceil(n / rows_per_block) * n rounded up to 64) + ceil(n / strip_cols) * n.
+ * 0 with an error message for a bad dtype or n.  No GPU needed. */
+uint64_t st_pair_scratch(int dtype, unsigned int n);
+/* The launch shape the kernels were built with ("block=256 bytes_per_load=16
+ * rows_in_flight=8 strip_cols=1024,512 rows_per_block=32,64,128,256
+ * rows_from=1,2048,4096,16384 combine_left=serial combine_right=serial
+ * lds_rows=256 finish_block=64 prep_grid=2048 nt_from_mib=512
+ * launches_per_round=5": a workgroup owns rows_per_block rows by one strip, a
+ * lane 16 bytes of each row - loaded as one vector, or element by element
+ * when n * sizeof(element) is no multiple of 16 or a pointer is not 16-byte
+ * aligned - with 8 rows' loads issued before the first fma; strip_cols by
+ * dtype (f32, f64)); tools record it next to their numbers
+ * (tools/bench_pair.py).  No GPU needed. */
+const char* st_pair_shape_desc(void);
+
+/* ---------------------------------------------------------------------- */
 /* 4. step-level kernels (asynchronous on `stream`, a hipStream_t or NULL) */
 /* ---------------------------------------------------------------------- */
 
@@ -1463,6 +1558,49 @@ int st_mfree_left_round_f64(const double* d_mat0, const double* d_s_prev,
                             double* d_v_cur, double* d_scratch, unsigned int n,
                             double eps, unsigned int k, unsigned int max_itr,
                             unsigned int semantics, st_state* d_state,
+                            void* stream);
+
+/* The dense pair scheme, step by step (section 3j; what
+ * st_solve_device_pair_* runs).  d_mat / d_mat0: n x n row-major, read only;
+ * all vectors device [n]; d_scratch: st_pair_scratch(dtype, n) elements,
+ * 256-byte aligned, distinct from the vectors.
+ *   st_pair_sum_*         d_s_right[r] = sum_c A[r][c] and d_s_left[c] =
+ *     sum_r A[r][c] from ONE pass over the matrix, in st_pair_shape's orders
+ *     (launch 0: both s_0); only the partials' parts of d_scratch are used
+ *   st_mfree_pair_round_* launch k >= 1 of both sides, five launches:
+ *     k_csr_prep once per side (x_R / x_L to the start of d_scratch, max and
+ *     the stop test of that side's s_prev through its state, d_states[0] the
+ *     right side's, d_states[1] the left one's); k_pair_sweep reads the matrix
+ *     once and writes the column products of every row block and the row
+ *     products of every strip; k_left_finish once per side adds them and writes
+ *     s_next = t / x and v_cur = v_prev * (s_prev / m).  The left side's
+ *     s_next, v_cur and state are bit for bit st_mfree_left_round_*'s; the
+ *     right side's v_cur and state are bit for bit st_mfree_round_*'s for the
+ *     same arguments.  A side whose state says an earlier round stopped gets
+ *     no write anywhere (its s_next, v_cur and partials stay as they are) and,
+ *     once both have, the matrix is not read.
+ * 16-byte loads when n * sizeof(element) is a multiple of 16 and d_mat and
+ * d_scratch are 16-byte aligned; otherwise element-wide (same bits).
+ * Nothing outside the n * n elements of the matrix is read. */
+int st_pair_sum_f32(const float* d_mat, float* d_s_right, float* d_s_left,
+                    float* d_scratch, unsigned int n, void* stream);
+int st_pair_sum_f64(const double* d_mat, double* d_s_right, double* d_s_left,
+                    double* d_scratch, unsigned int n, void* stream);
+int st_mfree_pair_round_f32(const float* d_mat0, const float* d_s_prev_right,
+                            float* d_s_next_right, const float* d_v_prev_right,
+                            float* d_v_cur_right, const float* d_s_prev_left,
+                            float* d_s_next_left, const float* d_v_prev_left,
+                            float* d_v_cur_left, float* d_scratch, unsigned int n,
+                            float eps, unsigned int k, unsigned int max_itr,
+                            unsigned int semantics, st_state* d_states /* [2] */,
+                            void* stream);
+int st_mfree_pair_round_f64(const double* d_mat0, const double* d_s_prev_right,
+                            double* d_s_next_right, const double* d_v_prev_right,
+                            double* d_v_cur_right, const double* d_s_prev_left,
+                            double* d_s_next_left, const double* d_v_prev_left,
+                            double* d_v_cur_left, double* d_scratch, unsigned int n,
+                            double eps, unsigned int k, unsigned int max_itr,
+                            unsigned int semantics, st_state* d_states /* [2] */,
                             void* stream);
 
 /* The sparse (CSR) scheme, step by step (what st_solve_csr runs); `csr` is a
